@@ -6,16 +6,20 @@ Workload (BASELINE.json configs[1]): 2-D FFT -> PSD -> autocorrelation on a 256-
 One "step" = one pass of b4d_psd_autocorr2d over the whole stack (PSD + autocorrelation
 written for every frame).  Metric: frames/s (whole job, all ranks), plus
   * roofline: the dominant kernel (column FFT/PSD/inverse) priced by HIP events inside the
-    timed region, against the 8 TB/s HBM roof (DESIGN.md states the byte accounting);
+    timed region, against the 8 TB/s HBM roof (DESIGN.md states the byte accounting).
+A plain run does only that: set-up, warm-up, the K timed steps, the outputs of the last step
+(--dump-outputs DIR) and the JSON line.  --full adds, after the timed region:
   * cpu_baseline: the NumPy oracle (port of the reference's fft2d + psd2d + autocorr2d calls)
-    timed on the host cores of this box on a bounded sample;
+    timed on the host cores of this box on a bounded sample (--no-cpu leaves it out);
   * secondary: the other BASELINE.json configs, measured AFTER the timed region of the headline
     (they never touch `value`): cfg3 phase-correlation tracking (1024^2), cfg4 temporal statistics
     (this rank's 2048^2 shard + ONE all-reduce over RCCL when --gpus N > 1) and cfg5 Wiener
     deconvolution (4096^2, sigma 1.5), each with its SURVEY.md §8(d) byte model, the fraction of the
-    8 TB/s roof and the error against the oracle on a small sample.
+    8 TB/s roof and the error against the oracle on a small sample (--no-secondary leaves it out).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/   # + the last step's PSD / autocorrelation
+    python bench.py --gpus 1 --full                                       # + secondary configs and CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 from __future__ import annotations
@@ -350,11 +354,40 @@ def parse_args(argv=None):
     ap.add_argument("--preheat", type=float, default=0.6,
                     help="seconds of untimed passes BEFORE the W warm-up steps: the first process on an idle GPU runs the column and "
                          "inverse row kernels 6-7 %% slower for its first ~0.2 s (profiles/r03_placement.txt)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the fft2d / cfg3 / cfg4 / cfg5 block after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the CPU baseline and the secondary fft2d / cfg3 / cfg4 / cfg5 block "
+                         "(off by default: a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32): frame 0 of the PSD and of the "
+                         "autocorrelation in full, and a fixed seeded sample of both over the whole stack")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave out the CPU baseline and the oracle checks")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the fft2d / cfg3 / cfg4 / cfg5 block")
     ap.add_argument("--spawn-check", action="store_true",
                     help="rendezvous only: every rank joins the host-side (gloo) group, rank 0 prints what it saw; no GPU call")
     return ap.parse_args(argv)
+
+
+DUMP_SAMPLE = 1 << 20          # elements of each sampled output (4 MiB as float32)
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, outdir: str, psd, ac) -> list:
+    """What a caller of the timed path receives, as float32 .npy files (42 MB in all at the default stack): frame 0 of
+    the PSD and of the autocorrelation, and both at the same DUMP_SAMPLE flat indices drawn once from DUMP_SEED over the
+    whole (T, N, N) stack (sorted, duplicates dropped).  Same arguments -> same indices, same inputs."""
+    os.makedirs(outdir, exist_ok=True)
+    total = int(psd.numel())
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, total, size=min(DUMP_SAMPLE, total), dtype=np.int64))
+    idx_dev = torch.from_numpy(idx).to(psd.device)
+    arrays = {"psd_frame0": psd[0], "autocorr_frame0": ac[0],
+              "psd_sample": psd.reshape(-1).index_select(0, idx_dev), "autocorr_sample": ac.reshape(-1).index_select(0, idx_dev)}
+    written = []
+    for name, t in arrays.items():
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, t.detach().to(torch.float32).cpu().numpy())
+        written.append(path)
+    return written
 
 
 def free_port() -> int:
@@ -415,6 +448,8 @@ def main(argv=None):
     args = parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, argv))      # nothing below runs in the parent: it never sees the GPU
 
@@ -522,6 +557,9 @@ def main(argv=None):
     # sanity on the product of the timed region (not a parity test): peak == 1 at the centre of every frame
     centre = ac[:, N // 2, N // 2]
     ok = bool(torch.all(centre == 1.0).item()) and bool(torch.isfinite(psd[0]).all().item())
+    if args.dump_outputs and rank == 0:     # rank 0's shard: the last timed step's PSD and autocorrelation, before anything reuses them
+        for path in dump_outputs(torch, args.dump_outputs, psd, ac):
+            print(f"bench.py: wrote {path}", file=sys.stderr)
 
     # after the timed region, N = 1 only: the same K steps once more on the workspace b4d_plan_tune keeps out of --tune-compare
     # candidates -- reported beside `value` so that the placement lottery is visible in the line, never as `value`
@@ -554,7 +592,7 @@ def main(argv=None):
 
     secondary = None
     frames_c4 = T
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         cpu = not args.no_cpu
         secondary = {"note": "measured after the timed region of the headline; never part of `value`; HBM roof 8 TB/s, copy ceiling "
                              "6.29 TB/s; frac_model prices SURVEY.md §8(d)'s byte models, frac_moved the bytes this implementation moves"}
@@ -657,7 +695,7 @@ def main(argv=None):
             line["plan_tune_comparison"] = tune_cmp
         if secondary is not None:
             line["secondary"] = secondary
-        if not args.no_cpu and world == 1:     # the CPU leg is timed at N = 1 only (it would idle the other ranks)
+        if args.full and not args.no_cpu and world == 1:     # the CPU leg is timed at N = 1 only (it would idle the other ranks)
             line["cpu_baseline"] = cpu_baseline(N, args.cpu_frames)
         emit(line)
     if world > 1:

@@ -44,3 +44,38 @@ def test_a_failing_rank_fails_the_job():
     r = _run(["--gpus", "2", "--spawn-check"], {"B4D_BENCH_TEST_FAIL_RANK": "1"})
     assert r.returncode != 0 and "ranks failed" in r.stderr
     assert "spawn_check" not in r.stdout
+
+
+def test_plain_run_is_headline_only_and_dumps_are_reproducible(tmp_path):
+    # a plain run leaves the secondary legs and the CPU baseline to --full; --dump-outputs writes float32 .npy files, the same
+    # bytes for the same outputs, and stays under 64 MB at the default stack (checked here on CPU tensors: no GPU)
+    code = f"""
+import json, os, sys
+import numpy as np, torch
+sys.path.insert(0, {ROOT!r})
+import bench
+plain, full = bench.parse_args(["--gpus", "1", "--steps", "3", "--warmup", "1"]), bench.parse_args(["--full"])
+g = torch.Generator().manual_seed(5)
+psd, ac = torch.rand((3, 64, 64), generator=g), torch.rand((3, 64, 64), generator=g)
+a = bench.dump_outputs(torch, {str(tmp_path / "a")!r}, psd, ac)
+b = bench.dump_outputs(torch, {str(tmp_path / "b")!r}, psd, ac)
+same = all(np.load(x).tobytes() == np.load(y).tobytes() for x, y in zip(a, b))
+dtypes = sorted({{str(np.load(x).dtype) for x in a}})
+frame0 = np.array_equal(np.load(a[0]), psd[0].numpy())
+default_bytes = 2 * 4 * bench.N * bench.N + 2 * 4 * min(bench.DUMP_SAMPLE, bench.FRAMES_PER_GPU * bench.N * bench.N)
+print(json.dumps({{"plain_full": plain.full, "full": full.full, "steps": plain.steps, "dump": plain.dump_outputs,
+                  "names": [os.path.basename(x) for x in a], "same": same, "dtypes": dtypes, "frame0": frame0,
+                  "default_bytes": default_bytes}}))
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["plain_full"] is False and d["full"] is True and d["steps"] == 3 and d["dump"] is None
+    assert sorted(d["names"]) == ["autocorr_frame0.npy", "autocorr_sample.npy", "psd_frame0.npy", "psd_sample.npy"]
+    assert d["same"] and d["dtypes"] == ["float32"] and d["frame0"]
+    assert d["default_bytes"] <= 64 * 10**6
+
+
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

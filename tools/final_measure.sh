@@ -3,11 +3,12 @@
 # counters in their own passes.  Everything lands in gpurun_out/final/.
 O=$GRAFT_REPO_ROOT/gpurun_out/final
 mkdir -p $O
+R=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 cd $GRAFT_REPO_ROOT
-python3 bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+python3 bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
 tail -c 600 $O/bench.json; echo
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $GRAFT_REPO_ROOT/bench.py --no-cpu > $O/stats.json 2> $O/stats.err < /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 "$R/bench.py" --full --no-cpu > $O/stats.json 2> $O/stats.err < /dev/null
 cd $GRAFT_REPO_ROOT
 bash tools/pmc_run.sh $O/pmc_fetch FETCH_SIZE < /dev/null
 bash tools/pmc_run.sh $O/pmc_write WRITE_SIZE < /dev/null

@@ -6,11 +6,11 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-# 1. the driver's line (default invocation) and the same command under rocprofv3 --kernel-trace --stats
-python3 bench.py > $O/bench.json 2> $O/bench.err < /dev/null
+# 1. the full bench line (--full: secondary configs and CPU baseline) and the same command under rocprofv3 --kernel-trace --stats
+python3 bench.py --full > $O/bench.json 2> $O/bench.err < /dev/null
 tail -c 300 $O/bench.json; echo
 cd /tmp && export TMPDIR=/tmp PYTHONPATH=$R
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu > $O/bench_under_rocprof.json 2> $O/stats.err < /dev/null
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu > $O/bench_under_rocprof.json 2> $O/stats.err < /dev/null
 f=$(find $O/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv
 # 2. HBM traffic of the headline kernels (FETCH_SIZE / WRITE_SIZE in passes of their own)
 cd $R
