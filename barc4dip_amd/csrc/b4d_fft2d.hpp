@@ -32,6 +32,7 @@
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
 #include "b4d_fft.hpp"
+#include "b4d_peak.hpp"
 
 // Translation units that build a kernel with their own compiler flags (b4d_passes.hpp) define B4D_UNIT_TAG before including
 // this header: the tag is a template argument of the kernels they launch, so that their instantiations are symbols of their
@@ -612,14 +613,6 @@ struct RowOutArgs {
 };
 
 enum RowOutMode { C2R_OUT = 0, C2R_PEAK = 1, C2R_MAG = 2, C2R_ROWS = 3 };
-
-// (value, flat index) arg-max with NumPy's first-occurrence rule: larger value wins, ties go to the lower index
-__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-        v = ov;
-        i = oi;
-    }
-}
 
 // grid (ceil(ny/2/SEQ), batch) -- or (1, batch) for C2R_PEAK; block T*SEQ.
 //   C2R_OUT   shifted real output, scaled (flags & NORM_PEAK: by 1/peak[frame], zero lag forced to 1)

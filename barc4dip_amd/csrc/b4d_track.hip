@@ -11,6 +11,7 @@
 #include <cstring>
 
 #include "b4d_fft2d.hpp"
+#include "b4d_peak.hpp"
 #include "b4d_select.hpp"
 #include "b4d_wiener_mr.hpp"
 
@@ -222,32 +223,8 @@ struct FinArgs {
 __device__ inline void track_finish(const FinArgs& p, size_t pair, const float* __restrict__ mag, int mny, int mnx, int oy, int ox,
                                     float bv, int bi, float med) {
     const int mi = bi / mnx, mj = bi % mnx;
-    const double peak = (double)bv;
-    const double snr = fabs(peak) / ((double)med + p.eps);
-    double dy = (double)(mi - oy), dx = (double)(mj - ox);
-    if (p.subpixel && mi > 0 && mi < mny - 1 && mj > 0 && mj < mnx - 1) {
-        auto c = [&](int di, int dj) { return mag[(size_t)(mi + di) * mnx + (mj + dj)]; };
-        const float c00 = c(0, 0);
-        const float gy = __fdiv_rn(__fsub_rn(c(1, 0), c(-1, 0)), 2.0f);
-        const float hyy = __fsub_rn(__fadd_rn(c(1, 0), c(-1, 0)), __fmul_rn(2.0f, c00));
-        const float gx = __fdiv_rn(__fsub_rn(c(0, 1), c(0, -1)), 2.0f);
-        const float hxx = __fsub_rn(__fadd_rn(c(0, 1), c(0, -1)), __fmul_rn(2.0f, c00));
-        const float hxy = __fdiv_rn(__fadd_rn(__fsub_rn(__fsub_rn(c(1, 1), c(1, -1)), c(-1, 1)), c(-1, -1)), 4.0f);
-        const float det = __fsub_rn(__fmul_rn(hxx, hyy), __fmul_rn(hxy, hxy));
-        if (det != 0.0f) {
-            const float inv = __fdiv_rn(1.0f, det);
-            // NOTE the reference's swapped corrections (tracking.py:372-373), reproduced on purpose
-            const float di = __fmul_rn(-__fsub_rn(__fmul_rn(hyy, gx), __fmul_rn(hxy, gy)), inv);
-            const float dj = __fmul_rn(-__fsub_rn(__fmul_rn(hxx, gy), __fmul_rn(hxy, gx)), inv);
-            dy += (double)di;
-            dx += (double)dj;
-        }
-    }
-    double* o = p.out + pair * 4;
-    o[0] = dy;
-    o[1] = dx;
-    o[2] = peak;
-    o[3] = snr;
+    auto c = [&](int di, int dj) { return mag[(size_t)(mi + di) * mnx + (mj + dj)]; };
+    peak_finish(c, mi, mj, mny, mnx, oy, ox, bv, med, p.subpixel, p.eps, p.out + pair * 4);
     if (p.peak_ij) {
         p.peak_ij[pair * 2] = mi;
         p.peak_ij[pair * 2 + 1] = mj;

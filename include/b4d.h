@@ -151,6 +151,22 @@ int b4d_template_match(b4d_plan* plan, const float* images, int nimg, const floa
                        const int32_t* pair_tpl, int npairs, int img_h, int img_w, int zscore_image, int subpixel, double eps,
                        double* out, int32_t* peak_ij, void* stream);
 
+/* Dense NCC displacement map (barc4dip_amd.signal.displacement_map): for every pair z (reference frame pair_ref[z], image
+ * frame pair_img[z]) and every window of the grid y0 = search_y + k * step_y (all k with y0 + win_y + search_y <= h; likewise
+ * for x) the result of template_matching(ref[y0:y0+win_y, x0:x0+win_x], img[y0-search_y:y0+win_y+search_y, x0-search_x:...],
+ * slices_yx=(slice(search_y, search_y+win_y), slice(search_x, search_x+win_x))): zero-mean NCC over the
+ * (2 search_y + 1) x (2 search_x + 1) local shifts, first-occurrence arg-max, peak, snr = |peak| / (median |ncc| + eps),
+ * 3x3 Taylor step (swapped corrections included).  zscore_image != 0: each search box is z-scored ("opencv", tracking.py:157);
+ * 0: raw box ("skimage").  Direct space, one workgroup per window, one launch for all pairs, on `stream`.
+ * ref (nref, h, w), img (nimg, h, w): DEVICE float32 frames.  pair_ref, pair_img (npairs,): HOST int32 indices.
+ * out: DEVICE (npairs, gy, gx, 4) float64 {dy, dx, peak, snr}; peak_ij: DEVICE (npairs, gy, gx, 2) int32 arg-max in the map,
+ * or null.  Limits: 1 <= win <= 128 and 1 <= search <= 32 per axis (B4D_ESIZE beyond), step >= 1, at least one window
+ * (B4D_EINVAL otherwise), gy and npairs <= 65535.                                                                          */
+int b4d_displacement_map(const float* ref, int nref, const float* img, int nimg, const int32_t* pair_ref,
+                         const int32_t* pair_img, int npairs, int h, int w, int win_y, int win_x, int step_y, int step_x,
+                         int search_y, int search_x, int zscore_image, int subpixel, double eps, double* out, int32_t* peak_ij,
+                         void* stream);
+
 /* Temporal per-pixel statistics (io/rw.py:129-132 for the mean).
  * accumulate: sum_x += sum_t x, sum_xx += sum_t x^2 over `nframes` frames of npix pixels
  * (float64 accumulators, caller zero-initialises; any npix / alignment).  finalize: mean, var (ddof 0),
