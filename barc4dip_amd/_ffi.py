@@ -56,6 +56,9 @@ SIGNATURES = {
     "b4d_phase_correlation": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _d, _vp, _vp, _vp]),
     "b4d_template_match": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     "b4d_displacement_map": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "b4d_spline_prefilter": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "b4d_warp_dense": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _vp, _vp]),
+    "b4d_warp_grid": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _i, _i, _i, _d, _d, _d, _d, _vp, _vp]),
     "b4d_temporal_accumulate": (_i, [_vp, _i, _sz, _vp, _vp, _vp]),
     "b4d_temporal_finalize": (_i, [_vp, _vp, _d, _sz, _vp, _vp, _vp, _vp]),
     "b4d_temporal_accumulate_range": (_i, [_vp, _i, _sz, _sz, _sz, _vp, _vp, _vp]),

@@ -347,7 +347,7 @@ extern "C" int b4d_displacement_map(const float* ref, int nref, const float* img
     a.gy = gy;
     a.gx = gx;
     a.zscore = zscore_image ? 1 : 0;
-    a.subpixel = subpixel ? 1 : 0;
+    a.subpixel = subpixel == 2 ? 2 : (subpixel ? 1 : 0);
     a.eps = eps;
     a.nch = (2 * search_x + 1 + RX - 1) / RX;
     a.wxp = (win_x + RX - 1) / RX * RX;

@@ -16,7 +16,7 @@ __device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi)
 // One lane: peak, snr = |peak| / (median + eps) and the sub-pixel shift of the arg-max (mi, mj) of an mny x mnx map,
 // op for op like tracking.py:314-375 (float32 scalars, no contraction).  c(di, dj) returns the map value at
 // (mi + di, mj + dj); it is only called for interior peaks.  Shifts are counted from (oy, ox).
-// o[0..3] = {dy, dx, peak, snr}.
+// subpixel: 0 none, 1 the reference's Taylor step, 2 the Newton step.  o[0..3] = {dy, dx, peak, snr}.
 template <class MapAt>
 __device__ inline void peak_finish(MapAt c, int mi, int mj, int mny, int mnx, int oy, int ox, float bv, float med, int subpixel,
                                    double eps, double* o) {
@@ -33,11 +33,12 @@ __device__ inline void peak_finish(MapAt c, int mi, int mj, int mny, int mnx, in
         const float det = __fsub_rn(__fmul_rn(hxx, hyy), __fmul_rn(hxy, hxy));
         if (det != 0.0f) {
             const float inv = __fdiv_rn(1.0f, det);
-            // NOTE the reference's swapped corrections (tracking.py:372-373), reproduced on purpose
+            // NOTE the reference's swapped corrections (tracking.py:372-373), reproduced on purpose for subpixel == 1;
+            // subpixel == 2 ("newton", displacement maps only) puts each correction on its own axis
             const float di = __fmul_rn(-__fsub_rn(__fmul_rn(hyy, gx), __fmul_rn(hxy, gy)), inv);
             const float dj = __fmul_rn(-__fsub_rn(__fmul_rn(hxx, gy), __fmul_rn(hxy, gx)), inv);
-            dy += (double)di;
-            dx += (double)dj;
+            dy += (double)(subpixel == 2 ? dj : di);
+            dx += (double)(subpixel == 2 ? di : dj);
         }
     }
     o[0] = dy;

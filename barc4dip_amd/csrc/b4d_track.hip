@@ -1092,7 +1092,7 @@ static int wmr_phase_correlation(b4d_plan* pl, const float* images, int nimg, co
         fa.ny = ny;
         fa.nx = nx;
         fa.nblk = qpf;
-        fa.subpixel = subpixel;
+        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
         fa.eps = eps;
         if ((rc = launch_track_fin2(fa, msel, pred, np, st))) return rc;
         if ((rc = launch_track_fin_rest(fa, msel, np, st))) return rc;
@@ -1166,7 +1166,7 @@ static int general_phase_correlation(b4d_plan* pl, const float* images, int nimg
         fa.ny = ny;
         fa.nx = nx;
         fa.nblk = nblk;
-        fa.subpixel = subpixel;
+        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
         fa.eps = eps;
         if ((rc = launch_track_fin(fa, np, st))) return rc;
         B4D_HIP(hipGetLastError());
@@ -1382,7 +1382,7 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
         fa.ny = ny;
         fa.nx = nx;
         fa.nblk = nblk;
-        fa.subpixel = subpixel;
+        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
         fa.eps = eps;
         fa.partial_map = nomap ? 1 : 0;
         if ((rc = launch_track_fin2(fa, msel, pred, np, ls))) return rc;
@@ -1580,7 +1580,7 @@ int b4d_template_match(b4d_plan* pl, const float* images, int nimg, const float*
             fa.ny = ny;
             fa.nx = nx;
             fa.nblk = nblk;
-            fa.subpixel = subpixel;
+            fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
             fa.eps = eps;
             if (expect) {   // passes 2-3 of the select on the gathered bin; whoever is left takes the whole select on its map
                 FinArgs fg = fa;

@@ -68,17 +68,29 @@ def _shape(a):
     return tuple(int(s) for s in a.shape) if D.is_tensor(a) else np.shape(a)
 
 
-def displacement_map(reference, images, *, window=31, step=None, search=8, backend: str = "opencv", subpixel: bool = True,
+def _subpixel_code(subpixel) -> int:
+    if isinstance(subpixel, str):
+        if subpixel != "newton":
+            raise ValueError(f'subpixel must be True, False or "newton", got {subpixel!r}')
+        return 2
+    return int(bool(subpixel))
+
+
+def displacement_map(reference, images, *, window=31, step=None, search=8, backend: str = "opencv", subpixel=True,
                      eps: float = 1e-9, return_tensors: bool = False) -> dict:
     """NCC displacement map of ``images`` against ``reference`` on a regular window grid.
 
     reference (H, W) with images (H, W) or (T, H, W), or reference (T, H, W) paired frame by frame with images (T, H, W)
     (incremental tracking: ``displacement_map(stack[:-1], stack[1:])``).  NumPy arrays of any real dtype or ROCm tensors.
     ``window``, ``step``, ``search``: int or (y, x); ``step=None`` is ``window // 2``.
+    ``subpixel``: True is the reference's 3x3 Taylor step, which puts the y correction on dx and the x correction on dy
+    (kept for parity with ``template_matching``); ``"newton"`` is the same step with each correction on its own axis, the
+    field that ``preprocessing.distortion.correct_distortion`` needs; False keeps integer shifts.
     Returns {"dy", "dx", "peak", "snr": float64 (gy, gx) or (T, gy, gx); "y", "x": window centres; "meta": {...}};
     with ``return_tensors=True`` the four maps are device tensors."""
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS}, got {backend!r}")
+    sub = _subpixel_code(subpixel)
     rs, ims = _shape(reference), _shape(images)
     if len(rs) not in (2, 3) or len(ims) not in (2, 3):
         raise ValueError(f"reference and images must be (H, W) or (T, H, W), got {rs} and {ims}")
@@ -102,7 +114,7 @@ def displacement_map(reference, images, *, window=31, step=None, search=8, backe
     out = torch.empty((nimg, gy, gx, 4), dtype=torch.float64, device=img.device)
     _ffi.check(_ffi.lib().b4d_displacement_map(
         D.ptr(ref), nref, D.ptr(img), nimg, pair_ref.ctypes.data_as(_ffi.C.c_void_p), pair_img.ctypes.data_as(_ffi.C.c_void_p),
-        nimg, H, W, wy, wx, sty, stx, sy, sx, int(backend == "opencv"), int(bool(subpixel)), float(eps), D.ptr(out), None,
+        nimg, H, W, wy, wx, sty, stx, sy, sx, int(backend == "opencv"), sub, float(eps), D.ptr(out), None,
         _ffi.stream_ptr()))
     if len(ims) == 2:
         out = out[0]

@@ -156,7 +156,8 @@ int b4d_template_match(b4d_plan* plan, const float* images, int nimg, const floa
  * for x) the result of template_matching(ref[y0:y0+win_y, x0:x0+win_x], img[y0-search_y:y0+win_y+search_y, x0-search_x:...],
  * slices_yx=(slice(search_y, search_y+win_y), slice(search_x, search_x+win_x))): zero-mean NCC over the
  * (2 search_y + 1) x (2 search_x + 1) local shifts, first-occurrence arg-max, peak, snr = |peak| / (median |ncc| + eps),
- * 3x3 Taylor step (swapped corrections included).  zscore_image != 0: each search box is z-scored ("opencv", tracking.py:157);
+ * 3x3 Taylor step for subpixel = 1 (swapped corrections included, as the reference), the same step with each correction on
+ * its own axis for subpixel = 2 (Newton), none for 0.  zscore_image != 0: each search box is z-scored ("opencv", tracking.py:157);
  * 0: raw box ("skimage").  Direct space, one workgroup per window, one launch for all pairs, on `stream`.
  * ref (nref, h, w), img (nimg, h, w): DEVICE float32 frames.  pair_ref, pair_img (npairs,): HOST int32 indices.
  * out: DEVICE (npairs, gy, gx, 4) float64 {dy, dx, peak, snr}; peak_ij: DEVICE (npairs, gy, gx, 2) int32 arg-max in the map,
@@ -166,6 +167,27 @@ int b4d_displacement_map(const float* ref, int nref, const float* img, int nimg,
                          const int32_t* pair_img, int npairs, int h, int w, int win_y, int win_x, int step_y, int step_x,
                          int search_y, int search_x, int zscore_image, int subpixel, double eps, double* out, int32_t* peak_ij,
                          void* stream);
+
+/* Distortion correction (barc4dip_amd.preprocessing.distortion; the reference reserves it in preprocessing/distortion.py):
+ * out[t, y, x] = scipy.ndimage.map_coordinates(frame t, [y + dy(t, y, x), x + dx(t, y, x)], order, mode, cval) in float32.
+ * mode: 0 "nearest", 1 "reflect", 2 "mirror", 3 "constant" (cval where y + dy or x + dx lies outside [0, side - 1]).
+ * order: 0, 1, or 3 (cubic B-spline).  All on `stream`, one launch per pass for the whole stack.
+ * b4d_spline_prefilter: the order-3 coefficients of src (n, h, w) for `mode` into coef (n, h + 2 p, w + 2 p), p = 12 for
+ *   "nearest" (scipy's edge padding), else 0: separable truncated FIR sqrt(3) (sqrt(3) - 2)^|k|, |k| <= 14 (2.4e-8 of scipy's
+ *   recursive filter).  Limits: n <= 65535, h <= 262140, w + 2 p <= 16384 (B4D_ESIZE beyond).
+ * b4d_warp_dense / b4d_warp_grid: src is the frames (n, h, w) for order 0 and 1, the coefficients of b4d_spline_prefilter with
+ *   the SAME mode for order 3.  field_frames = 1: one field for every frame; = n: field plane t warps frame t.
+ *   dense: dy, dx (field_frames, h, w) per-pixel displacements.
+ *   grid: dy, dx (field_frames, gy, gx) at window centres y0 + i step_y, x0 + j step_x; the field at (y, x) is
+ *   map_coordinates(grid, [(y - y0) / step_y, (x - x0) / step_x], order=1, mode="nearest"), evaluated in the kernel.
+ *   Taps and weights come from the float32 displacement, not from a float32 absolute coordinate.  out (n, h, w).
+ *   Limits: n <= 65535, h <= 262140 (B4D_ESIZE); gy, gx >= 1, finite non-zero steps (B4D_EINVAL).                          */
+int b4d_spline_prefilter(const float* src, int n, int h, int w, int mode, float* coef, void* stream);
+int b4d_warp_dense(const float* src, int n, int h, int w, int order, int mode, float cval, const float* dy, const float* dx,
+                   int field_frames, float* out, void* stream);
+int b4d_warp_grid(const float* src, int n, int h, int w, int order, int mode, float cval, const float* dy, const float* dx,
+                  int field_frames, int gy, int gx, double y0, double step_y, double x0, double step_x, float* out,
+                  void* stream);
 
 /* Temporal per-pixel statistics (io/rw.py:129-132 for the mean).
  * accumulate: sum_x += sum_t x, sum_xx += sum_t x^2 over `nframes` frames of npix pixels
