@@ -28,19 +28,16 @@ def to_device_f32(a, *, ndim: tuple[int, ...]):
             raise NotImplementedError("complex input is not supported by the HIP path (real frames only).")
         if a.ndim not in ndim:
             raise ValueError(f"expected ndim in {ndim}, got {a.ndim}")
-        src_dtype = np.float32 if a.dtype in (torch.float32, torch.float16, torch.bfloat16) else np.float64
-        return a.to(device="cuda", dtype=torch.float32).contiguous(), True, src_dtype
+        return a.to(device="cuda", dtype=torch.float32).contiguous(), True, result_dtype(a)
     arr = np.asarray(a)
     if np.iscomplexobj(arr):
         raise NotImplementedError("complex input is not supported by the HIP path (real frames only).")
     if arr.ndim not in ndim:
         raise ValueError(f"expected ndim in {ndim}, got {arr.ndim}")
-    # NumPy's FFT promotes everything except float16 / float32 to double precision: outputs follow that dtype
-    src_dtype = np.float32 if arr.dtype in (np.float32, np.float16) else np.float64
-    if arr.nbytes >= _UPLOAD_MIN_BYTES and arr.flags.c_contiguous and arr.dtype.name in _UPLOAD_CODES and arr.dtype != np.float32:
-        return _upload_staged(arr), False, src_dtype
+    if staged_code(arr) is not None:
+        return _upload_staged(arr), False, result_dtype(arr)
     t = torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).to("cuda", non_blocking=False)
-    return t, False, src_dtype
+    return t, False, result_dtype(arr)
 
 
 # ---- large host arrays that are not float32 (the host -> HBM half): a host-side astype of detector words runs
@@ -49,11 +46,24 @@ def to_device_f32(a, *, ndim: tuple[int, ...]):
 # while the previous block is on the bus, and are converted to float32 on the device (b4d_to_f32: the same round-to-nearest
 # conversion as ndarray.astype).  8 x 2048^2 frames (tools/dev_upload.py): uint16 16.2 -> 2.4 ms, float64 21.4 -> 7.4 ms; float32
 # arrays keep the plain copy (2.7 ms against 3.3 staged: the runtime's own staging is as fast).  Everything stays on the caller's
-# stream.
+# stream.  Byte-swapped arrays (FITS, '>u2' .npy files) take the same route: the host threads copy into a NATIVE-order view of the
+# page-locked block, so NumPy swaps the bytes while copying and b4d_to_f32 always reads native words.  The swap costs little
+# (tools/dev_upload.py, fresh arrays): '>u2' 2.5 ms against 2.1 native, '>f8' 7.2 against 6.6, and '>f4' 4.0 staged against 24.2
+# through the plain route's single-threaded swapping astype -- so byte-swapped float32 is staged too.
 _UPLOAD_MIN_BYTES = 32 << 20
 _UPLOAD_BLOCK = 32 << 20
 _UPLOAD_CODES = {"uint8": 0, "uint16": 1, "int16": 2, "int32": 3, "uint32": 4, "float32": 5, "float64": 6}
 _upload_pool = None
+
+
+def staged_code(arr: np.ndarray):
+    """b4d_to_f32 code under which host array `arr` goes up through _upload_staged, or None for the plain route (host astype +
+    copy): C-contiguous arrays of _UPLOAD_MIN_BYTES and more whose dtype, in either byte order, is a detector word or float64.
+    Native float32 keeps the plain copy; byte-swapped float32 is staged (code 5), where the copy into the block swaps it."""
+    dt = arr.dtype
+    if arr.nbytes < _UPLOAD_MIN_BYTES or not arr.flags.c_contiguous or (dt.name == "float32" and dt.isnative):
+        return None
+    return _UPLOAD_CODES.get(dt.name)      # dtype names carry no byte order: '>u2' and '<u2' are both 'uint16'
 
 
 def _upload_staged(arr: np.ndarray):
@@ -65,6 +75,7 @@ def _upload_staged(arr: np.ndarray):
         _upload_pool = ThreadPoolExecutor(max_workers=4, thread_name_prefix="b4d-upload")
     lib = _ffi.lib()
     code, item = _UPLOAD_CODES[arr.dtype.name], arr.dtype.itemsize
+    native = arr.dtype.newbyteorder("=")   # the block holds native words whatever the caller's byte order
     flat = arr.reshape(-1)
     n = int(flat.size)
     out = torch.empty(arr.shape, dtype=torch.float32, device="cuda")
@@ -78,7 +89,7 @@ def _upload_staged(arr: np.ndarray):
         b, slot = min(n, a + per), k & 1
         if sent[slot] is not None:
             sent[slot].synchronize()        # the block's previous copy has left the page-locked buffer
-        host = pinned[slot].numpy()[:(b - a) * item].view(arr.dtype)
+        host = pinned[slot].numpy()[:(b - a) * item].view(native)
         q = max(1, -(-(b - a) // 4))
         list(_upload_pool.map(lambda lo: np.copyto(host[lo:lo + q], flat[a + lo:min(b, a + lo + q)]), range(0, b - a, q)))
         if code == 5:
@@ -165,7 +176,14 @@ def _download_staged(t, want):
 
 
 def result_dtype(a):
-    """Real dtype the reference's NumPy pipeline would return for input `a`: float32 for float16 / float32 input,
-    float64 for everything else (integers, bool, float64) -- numpy.fft promotes those to double precision."""
-    name = str(getattr(a, "dtype", "float64")).replace("torch.", "")
-    return np.float32 if name in ("float32", "float16", "bfloat16") else np.float64
+    """Real dtype the reference's NumPy pipeline would return for input `a` (np.fft.fft2(a).real.dtype): float32 for float16,
+    float32 and complex64 input (torch: also bfloat16), float64 for everything else -- numpy.fft promotes integers, bool and
+    float64 to double precision.  Decided by kind and item size, so byte order does not matter.  One deliberate exception:
+    long double input (float128 / complex256) gives float64 here where NumPy keeps long double (the device has no such type)."""
+    dt = getattr(a, "dtype", np.float64)
+    if is_tensor(a):
+        import torch
+
+        return np.float32 if dt in (torch.float32, torch.float16, torch.bfloat16, torch.complex64) else np.float64
+    dt = np.dtype(dt)
+    return np.float32 if (dt.kind == "f" and dt.itemsize <= 4) or (dt.kind == "c" and dt.itemsize <= 8) else np.float64

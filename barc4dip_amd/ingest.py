@@ -33,7 +33,8 @@ def iter_device_chunks(source, chunk_frames: int = 16):
     chunk = max(1, min(int(chunk_frames), T))
     name = np.dtype(source.dtype).name
     code = _DTYPE_CODES.get(name)
-    raw_dtype = np.dtype(source.dtype) if code is not None else np.dtype(np.float32)   # other dtypes: converted on the host
+    # the pinned buffer holds NATIVE-order words (np.copyto swaps a big-endian memmap while staging); other dtypes: converted on the host
+    raw_dtype = np.dtype(source.dtype).newbyteorder("=") if code is not None else np.dtype(np.float32)
     code = code if code is not None else _DTYPE_CODES["float32"]
     item = raw_dtype.itemsize
     copy_stream = torch.cuda.Stream()

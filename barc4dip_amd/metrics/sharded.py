@@ -137,7 +137,8 @@ def gather_series(local: np.ndarray, *, group=None) -> np.ndarray:
         return local
     world = dist.get_world_size(group)
     dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" else torch.device("cpu")
-    arr = np.ascontiguousarray(local)
+    arr = np.asarray(local)
+    arr = np.ascontiguousarray(arr, dtype=arr.dtype.newbyteorder("="))     # torch.from_numpy takes native byte order only
     n = torch.tensor([arr.shape[0]], dtype=torch.int64, device=dev)
     sizes = [torch.zeros_like(n) for _ in range(world)]
     dist.all_gather(sizes, n, group=group)

@@ -96,7 +96,8 @@ def fft2d_stack(stack, *, return_tensors: bool = False):
 def _c2c(frames, inverse: bool):
     """(B, ny, nx) complex frames through b4d_fft2d_c2c on a general-length plan -> complex64 device tensor."""
     torch = _ffi.require_gpu()
-    t = frames if D.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+    # torch.from_numpy takes native byte order only: a big-endian spectrum ('>c8', FITS) is swapped on the host first
+    t = frames if D.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames, dtype=frames.dtype.newbyteorder("=")))
     t = t.to(device="cuda", dtype=torch.complex64).contiguous()
     b, ny, nx = (int(v) for v in t.shape)
     pl = _ffi.get_plan(ny, nx, general=True)
@@ -111,8 +112,7 @@ def _is_complex(a) -> bool:
 
 
 def _complex_result_dtype(a):
-    name = str(getattr(a, "dtype", "complex128")).replace("torch.", "")
-    return np.complex64 if name == "complex64" else np.complex128
+    return np.complex64 if D.result_dtype(a) is np.float32 else np.complex128
 
 
 def fft2d(image, *, x=None, y=None, dx: float = 1.0, dy: float = 1.0, return_tensors: bool = False):

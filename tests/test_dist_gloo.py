@@ -90,3 +90,35 @@ def test_tracking_halo_and_frame0_broadcast(tmp_path, world, total):
         assert np.array_equal(g["f0"], stack[0])
         assert np.array_equal(g["prev"], stack[max(t0 - 1, 0)])
         assert np.array_equal(g["series"][:, 0], np.arange(total, dtype=np.float32))
+
+
+def _series_worker(rank, world, port, total, out_dir):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from barc4dip_amd.metrics.sharded import gather_series, shard_bounds
+
+    t0, t1 = shard_bounds(total, world, rank)
+    rows = np.arange(t0, t1, dtype=np.float64)[:, None] * np.array([1.0, -0.5, 3.25])
+    out = {}
+    for code in ("<f4", ">f4", ">f8", ">i8", ">i4"):
+        local = (rows + 2.0).astype(code)
+        out[code] = gather_series(local)
+        out["F" + code] = gather_series(np.asfortranarray(local))
+    np.savez(os.path.join(out_dir, f"s{rank}.npz"), **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+@pytest.mark.parametrize("world,total", [(2, 7)])
+def test_gather_series_any_byte_order(tmp_path, world, total):
+    """gather_series of byte-swapped (FITS-order) or Fortran-ordered shards: the values of the native-order gather, in the
+    native-order dtype."""
+    mp.spawn(_series_worker, args=(world, _free_port(), total, str(tmp_path)), nprocs=world, join=True)
+    rows = np.arange(total, dtype=np.float64)[:, None] * np.array([1.0, -0.5, 3.25]) + 2.0
+    for r in range(world):
+        g = np.load(tmp_path / f"s{r}.npz")
+        for code in ("<f4", ">f4", ">f8", ">i8", ">i4"):
+            want = rows.astype(code).astype(np.dtype(code).newbyteorder("="))
+            for key in (code, "F" + code):
+                assert g[key].dtype == want.dtype and np.array_equal(g[key], want), (r, key)

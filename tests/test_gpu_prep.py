@@ -152,6 +152,12 @@ def test_large_host_arrays_go_up_in_their_native_dtype(prep, dtype):
     # a non-contiguous view of a large array takes the ordinary route
     v = a[:, :, ::2]
     np.testing.assert_array_equal(D.to_device_f32(v, ndim=(3,))[0].cpu().numpy().view(np.uint32), v.astype(np.float32).view(np.uint32))
+    # the same values in the other byte order (FITS, '>u2' .npy files) are staged too: swapped while copied into the blocks
+    s = a.astype(a.dtype.newbyteorder("S"))
+    ts, _, src_s = D.to_device_f32(s, ndim=(3,))
+    assert src_s is src and tuple(ts.shape) == shape
+    np.testing.assert_array_equal(ts.cpu().numpy().view(np.uint32), a.astype(np.float32).view(np.uint32))
+    assert D.staged_code(s) == D._UPLOAD_CODES[dtype]
 
 
 def test_large_results_come_down_through_page_locked_blocks(prep):

@@ -1,5 +1,5 @@
 """dev: host -> device time of _device.to_device_f32 for 8 x 2048^2 stacks of several dtypes (staged native-dtype route against the
-plain astype + pageable copy)."""
+plain astype + pageable copy), native and byte-swapped."""
 import sys
 import time
 
@@ -10,7 +10,7 @@ sys.path.insert(0, ".")
 from barc4dip_amd import _device as D  # noqa: E402
 
 rng = np.random.default_rng(0)
-for dtype in ("float32", "uint16", "float64"):
+for dtype in ("float32", "uint16", "float64", ">f4", ">u2", ">f8"):     # big-endian: FITS, '>u2' .npy files
     a = (rng.random((8, 2048, 2048)) * 60000).astype(dtype)
     for route in ("staged", "plain"):
         D._UPLOAD_MIN_BYTES = (32 << 20) if route == "staged" else (1 << 60)
