@@ -201,7 +201,7 @@ __global__ void __launch_bounds__(256) k_temporal_fin(const double* __restrict__
     const double count = count_dev ? count_dev[0] : count_val;
     const double m = sx[i] / count;
     double v = sxx[i] / count - m * m;
-    v = v > 0.0 ? v : 0.0;
+    v = v < 0.0 ? 0.0 : v;   // rounding may leave a tiny negative; a NaN variance (NaN pixel, inf - inf) stays NaN
     if (mean) mean[i] = (float)m;
     if (var) var[i] = (float)v;
     if (contrast) contrast[i] = (float)(sqrt(v) / m);
@@ -389,7 +389,29 @@ __global__ void __launch_bounds__(256) k_sobel_fin(const double* __restrict__ pa
 // ------------------------------------------------------------------------------------ percentiles
 // np.nanpercentile(x, q) with the default linear interpolation (utils/range.py:44-54): for each q the two
 // bracketing order statistics are selected exactly; out = {lo value, hi value, fraction, n_valid} and the
-// caller finishes lo + (hi - lo) * t in float64 exactly like NumPy's _lerp.   grid (batch), block 1024.
+// caller finishes lo + (hi - lo) * t in float64 exactly like NumPy's _lerp.
+//
+// Rank and fraction both come from ONE number, NumPy's virtual index for method="linear" (alpha = beta = 1):
+//   vi = n*qf + (1 + qf*(1 - 1 - 1)) - 1,  qf = q/100,  lo = floor(vi) clamped to [0, n-1],  fraction = vi - floor(vi)
+// in NumPy's operation order with individually rounded operations: a contracted fma, or the algebraically equal
+// qf*(n-1), differs in the last bit next to integers and then brackets the wrong pair of order statistics.
+// hipcc contracts a*b + c by default, and in this toolchain __dmul_rn / __dadd_rn are the plain operators (contracted like
+// any other), so contraction is switched off for the block instead.
+__device__ __forceinline__ double pct_virtual_index(double q, unsigned n) {
+#pragma clang fp contract(off)
+    const double qf = q / 100.0;
+    const double a = (double)n * qf;
+    const double b = 1.0 + qf * (1.0 - 1.0 - 1.0);
+    const double s = a + b;
+    return s - 1.0;
+}
+__device__ __forceinline__ unsigned pct_rank(double vi, unsigned n) {   // n >= 1
+    const double f = floor(vi);
+    if (!(f > 0.0)) return 0u;
+    return f >= (double)(n - 1) ? n - 1 : (unsigned)f;
+}
+
+// grid (batch), block 1024.
 __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ frames, size_t npix, const double* __restrict__ q,
                                                       int nq, double* __restrict__ out) {
 #ifndef B4D_PCT_REP
@@ -416,9 +438,8 @@ __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ 
             if (threadIdx.x == 0) o[0] = o[1] = nan(""), o[2] = 0.0, o[3] = 0.0;
             continue;
         }
-        const double pos = q[iq] / 100.0 * (double)(n - 1);
-        unsigned lo = (unsigned)floor(pos);
-        if (lo > n - 1) lo = n - 1;
+        const double vi = pct_virtual_index(q[iq], n);
+        const unsigned lo = pct_rank(vi, n);
         const unsigned hi = lo + 1 < n ? lo + 1 : n - 1;
         unsigned nl, ne;
         const unsigned ka = radix_select<REP>(x, n_all, lo, hist, sh, nl, ne);
@@ -427,7 +448,7 @@ __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ 
         if (threadIdx.x == 0) {
             o[0] = (double)key2f(ka);
             o[1] = (double)key2f(kb);
-            o[2] = pos - (double)lo;
+            o[2] = vi - floor(vi);
             o[3] = (double)n;
         }
         __syncthreads();
@@ -506,11 +527,7 @@ __global__ void __launch_bounds__(64) k_pctm_pick(PctMulti p) {
     if (PASS == 0) {
         const unsigned n = total;
         unsigned lo = 0;
-        if (n > 0) {
-            const double pos = p.q[j] / 100.0 * (double)(n - 1);
-            lo = (unsigned)floor(pos);
-            if (lo > n - 1) lo = n - 1;
-        }
+        if (n > 0) lo = pct_rank(pct_virtual_index(p.q[j], n), n);
         kk = lo;
         if (lane == 0) {
             st[0] = 0;
@@ -592,13 +609,13 @@ __global__ void __launch_bounds__(64) k_pctm_out(PctMulti p) {
         o[3] = 0.0;
         return;
     }
-    const double pos = p.q[j] / 100.0 * (double)(n - 1);
+    const double vi = pct_virtual_index(p.q[j], n);
     const unsigned lo = st[2], hi = lo + 1 < n ? lo + 1 : n - 1;
     unsigned kb = st[0];
     if (hi != lo && st[1] + st[3] <= hi && st[5] != 0xffffffffu) kb = st[5];
     o[0] = (double)key2f(st[0]);
     o[1] = (double)key2f(kb);
-    o[2] = pos - (double)lo;
+    o[2] = vi - floor(vi);
     o[3] = (double)n;
 }
 
@@ -728,6 +745,8 @@ __global__ void k_psd_stats_mid(PsdStatArgs a, double* __restrict__ out, int* __
             cum += c;
         }
         out[(size_t)b * 8 + 7] = tot;  // masked total as accumulated by the histogram (diagnostic)
+    } else {
+        out[(size_t)b * 8 + 7] = nan("");   // f95 is defined for square maps only
     }
     ring[b] = r;
     below[b] = cum;
@@ -783,7 +802,8 @@ __global__ void k_psd_stats_fin(PsdStatArgs a, const int* __restrict__ ring, con
         cum += c;
     }
     (void)found;
-    out[(size_t)b * 8 + 7] = sqrt((double)r2) / (double)a.nx;
+    // no power inside the disc (an all-zero map): there is no 95 % radius
+    out[(size_t)b * 8 + 7] = tot > 0.0 ? sqrt((double)r2) / (double)a.nx : nan("");
 }
 
 }  // namespace b4d

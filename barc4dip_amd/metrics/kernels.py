@@ -56,11 +56,19 @@ def temporal_finalize(sum_x, sum_xx, count: float):
     return mean, var, con
 
 
+def finish_percentiles(lo, hi, frac):
+    """NumPy's ``_lerp`` on the raw outputs of b4d_percentiles: ``lo + (hi - lo) * frac``, taken from the upper end as
+    ``hi - (hi - lo) * (1 - frac)`` where ``frac >= 0.5``.  Pure NumPy (float64 arrays in, float64 array out); an infinite
+    bracketing value gives NaN, as it does in ``np.nanpercentile``."""
+    lo, hi, frac = (np.asarray(v, dtype=np.float64) for v in (lo, hi, frac))
+    with np.errstate(invalid="ignore", over="ignore"):
+        diff = hi - lo
+        return np.where(frac >= 0.5, hi - diff * (1.0 - frac), lo + diff * frac)
+
+
 def percentiles_batch(frames, q):
     """np.nanpercentile(frame, q) (linear interpolation) for every frame: (B, ...) -> (B, len(q)) float64 ndarray."""
     import ctypes as C
-
-    import numpy as np
 
     torch = _ffi.require_gpu()
     t, _, _ = D.to_device_f32(frames, ndim=(2, 3))
@@ -71,15 +79,8 @@ def percentiles_batch(frames, q):
     _ffi.check(_ffi.lib().b4d_percentiles(D.ptr(t), b, npix, qs.ctypes.data_as(C.c_void_p), int(qs.size), D.ptr(out),
                                           _ffi.stream_ptr()))
     r = out.cpu().numpy()
-    lo, hi, n = r[..., 0], r[..., 1], r[..., 3]
-    # NumPy's virtual index for method="linear" (alpha = beta = 1), same expression order as
-    # numpy.lib._function_base_impl._compute_virtual_index
-    qf = np.true_divide(qs, 100)[None, :]
-    vi = n * qf + (1.0 + qf * (1.0 - 1.0 - 1.0)) - 1.0
-    frac = vi - np.floor(vi)
-    diff = hi - lo
-    # NumPy's _lerp: a + diff*t, but b - diff*(1-t) for t >= 0.5
-    return np.where(frac >= 0.5, hi - diff * (1.0 - frac), lo + diff * frac)
+    # the kernel returns the fraction of the same virtual index that chose the bracketing pair: never recompute it here
+    return finish_percentiles(r[..., 0], r[..., 1], r[..., 2])
 
 
 def psd_stats_batch(psd):

@@ -247,8 +247,13 @@ int b4d_sta2_eigenvalues(const float* frames, int batch, int ny, int nx, double*
 
 /* utils/range.py:44-54 percentile_minmax_range / np.nanpercentile (linear interpolation): exact selection
  * of the two bracketing order statistics of the non-NaN pixels of every frame.  q: HOST array of nq (<= 16)
- * percentiles in [0, 100].  out: DEVICE (batch, nq, 4) float64 {x_lo, x_hi, fraction, n_valid}; the caller
- * finishes x_lo + (x_hi - x_lo) * fraction in float64.  Synchronises the stream.                          */
+ * percentiles in [0, 100].  out: DEVICE (batch, nq, 4) float64 {x_lo, x_hi, fraction, n_valid}.
+ * Rank and fraction come from NumPy's virtual index for method="linear", evaluated in NumPy's operation order with
+ * individually rounded operations: vi = n*qf + (1 + qf*(1 - 1 - 1)) - 1 with qf = q/100 and n = n_valid;
+ * x_lo = s[lo], lo = floor(vi) clamped to [0, n-1]; x_hi = s[min(lo + 1, n-1)]; fraction = vi - floor(vi).
+ * The caller finishes like NumPy's _lerp in float64 with THIS fraction (x_lo + (x_hi - x_lo) * fraction, or
+ * x_hi - (x_hi - x_lo) * (1 - fraction) for fraction >= 0.5); a fraction recomputed from another rank formula can
+ * belong to a different pair.  A frame without a non-NaN pixel gives {NaN, NaN, 0, 0}.  Synchronises the stream.  */
 int b4d_percentiles(const float* frames, int batch, size_t npix, const double* q, int nq, double* out, void* stream);
 
 /* maths/radial.py:101-169 radial_mean_interpolated: nr x ntheta polar samples, bilinear interpolation on the
@@ -258,7 +263,8 @@ int b4d_radial_profile(const float* maps, int batch, int ny, int nx, int nr, int
 
 /* metrics/speckles.py:669-817 bandwidth + metrics/sharpness.py:536-629 spectral_entropy from a shifted PSD
  * map (DC bin treated as zero).  out: DEVICE (batch, 8) float64 {S_disc, sum FR^2 P, sum FX^2 P, sum FY^2 P,
- * sum P^2 (all four over the inscribed frequency disc), S_all, sum P ln P (all bins), f95 (square maps)}.  */
+ * sum P^2 (all four over the inscribed frequency disc), S_all, sum P ln P (all bins), f95 (square maps; NaN when
+ * ny != nx)}.                                                                                                  */
 int b4d_psd_stats(const float* psd, int batch, int ny, int nx, double* out, void* stream);
 
 /* preprocessing/filters.py:17-289 deconvolve_psf, method="wiener" (BASELINE.json config 5).
