@@ -5,7 +5,8 @@
 #include "b4d_passes.hpp"
 
 namespace b4d {
-int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {
+int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, int ysplit) {
+    if (ysplit) return launch_col_ys(pl, a, batch, st);
     return dispatch_col<COL_PSD_AC>(pl, a, batch, st);
 }
 }  // namespace b4d

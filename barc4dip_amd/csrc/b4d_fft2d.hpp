@@ -18,6 +18,17 @@
 //   K3 row_c2r   rebuilds the two-row packing from the half spectra, one inverse FFT of length nx,
 //                shift + normalise -> two autocorrelation rows.
 //
+//
+// "ysplit" route (PSD + autocorrelation of 2048-row frames; option "ysplit" of b4d_set_option): the row passes
+// do one radix-2 stage of the column transform each, at no extra byte or launch.  With h = ny/2, w = exp(-2 pi i / ny):
+//   K1 row_r2c   transform p packs rows p and p + h; their half spectra A, B leave as A + B (even ky) and (A - B) w^p (odd ky),
+//                layout [frame][parity][ct][p][c] with 32-column tiles (the same bytes: two tile sets of h rows).
+//   K2 col       a workgroup owns a PARITY tile (32 columns x h rows, the same 256 KiB): the h-point transform gives F(2k + parity),
+//                PSD rows ky = 2k + parity are whole 128-B lines (+ mirror), the inverse gives E (even) or O (odd), rows 0..h/2 kept.
+//   K3 row_c2r   transform y in [0, h/2] reads row y of E and O, G(y) = E + conj(w^y) O and G(h - y) = conj(E - conj(w^y) O) ride
+//                the two-row packing; rows y, h - y and their point mirrors are written, every row once.
+//   k_nyq        unchanged (K1 still stores the plain Nyquist bins of both rows).
+//
 // All of them are HBM-bandwidth bound; see DESIGN.md for the byte accounting.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -112,14 +123,18 @@ struct RowSrc {
 #ifndef B4D_K1_ITER
 #define B4D_K1_ITER 1
 #endif
-template <int NX, int SEQ, bool SRC, int ITER = 1>
+// YS ("ysplit" route, ny = 2048): transform p packs rows p and p + ny/2 and applies the first radix-2 stage of the COLUMN
+// transform to their half spectra A, B: A + B -> row p of the even-ky tile set, (A - B) w^p -> row p of the odd one
+// (w^p = tw_y[p], uniform per transform).  Layout [frame][parity][ct][p][c], ct_w columns per tile.
+template <int NX, int SEQ, bool SRC, int ITER = 1, bool YS = false>
 __global__ void __launch_bounds__((NX / E16) * SEQ)
 k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __restrict__ nyq_rows,
-          const float2* __restrict__ tw, int ny, int ct_w, const RowSrc* __restrict__ srcs) {
+          const float2* __restrict__ tw, int ny, int ct_w, const RowSrc* __restrict__ srcs, const float2* __restrict__ tw_y) {
     using G = RowGeom<NX>;
     constexpr int T = G::T, E = E16;
     constexpr bool WV = T <= 64;   // one transform = (part of) one wavefront: no workgroup barriers (fft_sync)
     static_assert(ITER == 1 || !SRC, "ROI sources run one group per workgroup");
+    static_assert(!YS || !SRC, "the ysplit pairing takes full frames");
     __shared__ float2 lds_all[SEQ * G::LDS_ELEMS];
     const int seq = threadIdx.x / T, u = threadIdx.x % T;
     const size_t frame = blockIdx.y;
@@ -154,8 +169,8 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
                 v[j].y = (inb && inx) ? (r1[x] - sd.mean) * inv : 0.f;
             }
         } else {
-            const float* r0 = in + (frame * ny + 2 * (size_t)pair) * NX;
-            const float* r1 = r0 + NX;
+            const float* r0 = in + (frame * ny + (YS ? 1 : 2) * (size_t)pair) * NX;
+            const float* r1 = r0 + (YS ? (size_t)(ny / 2) * NX : (size_t)NX);
 #pragma unroll
             for (int j = 0; j < E; ++j) v[j] = make_float2(r0[u + T * j], r1[u + T * j]);
         }
@@ -173,6 +188,8 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
         for (int j = 0; j < E; ++j) lds[u + T * j] = v[j];
         fft_sync<WV>();
         if (live) {
+            float2 wp = make_float2(1.f, 0.f);
+            if (YS) wp = tw_y[pair];
 #pragma unroll
             for (int j = 0; j < E / 2; ++j) {
                 const int k = u + T * j;
@@ -183,12 +200,18 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
                     const float2 zn = lds[NX / 2];
                     a = make_float2(z.x, 0.f);
                     b = make_float2(z.y, 0.f);
-                    nyq_rows[frame * ny + 2 * pair] = zn.x;
-                    nyq_rows[frame * ny + 2 * pair + 1] = zn.y;
+                    nyq_rows[frame * ny + (YS ? pair : 2 * pair)] = zn.x;
+                    nyq_rows[frame * ny + (YS ? pair + ny / 2 : 2 * pair + 1)] = zn.y;
                 }
-                const size_t o = spec_index(frame, nt, ny, ct_w, 2 * pair, k);
-                spec[o] = a;
-                spec[o + ct_w] = b;  // next row of the same tile
+                if (YS) {
+                    const size_t o = spec_index(2 * frame, nt, ny / 2, ct_w, pair, k);
+                    spec[o] = cadd(a, b);
+                    spec[o + (size_t)(ny / 2) * (NX / 2)] = cmul(csub(a, b), wp);  // same row of the odd-ky tile set
+                } else {
+                    const size_t o = spec_index(frame, nt, ny, ct_w, 2 * pair, k);
+                    spec[o] = a;
+                    spec[o + ct_w] = b;  // next row of the same tile
+                }
             }
         }
     }
@@ -243,10 +266,14 @@ struct ColArgs {
 // __launch_bounds__(THREADS, 4) caps every variant at 128 VGPRs so that smaller NY run several workgroups per CU.
 // SPLIT workgroups share one memory tile (each takes CT / SPLIT adjacent columns of it): the layout keeps whole
 // 128-B lines per row while two 512-lane workgroups fit one CU and overlap each other's memory and butterfly phases.
-template <int NY, int SPLIT = 1>
+// YS ("ysplit" route of 2048-row frames, NY = 1024 here): the row passes do one radix-2 stage of the column transform, a
+// workgroup owns one PARITY tile (the even or the odd ky of CT columns): CPT = 16 -> CT = 32 columns x 1024 rows, the same
+// 256 KiB in 1024 lanes, whole 128-B lines in every direct PSD store.  (16-column parity tiles, 512 lanes and two workgroups
+// per CU, were measured 20 % slower on the column pass: DESIGN.md §8.1.)
+template <int NY, int SPLIT = 1, int YS = 0>
 struct ColCfg {
     static constexpr int NC = 2;
-    static constexpr int CPT = (NY == 4096 ? 4 : 8) / SPLIT;
+    static constexpr int CPT = (NY == 4096 ? 4 : 8) / SPLIT * (YS ? 2 : 1);
     static constexpr int CT = NC * CPT * SPLIT;   // columns per MEMORY tile
     static constexpr int THREADS = CPT * (NY / E16);
     static constexpr int WAVES_PER_EU = THREADS >= 256 ? 4 : 1;
@@ -297,9 +324,11 @@ __device__ __forceinline__ void store_cols(float2* __restrict__ rowp, const floa
 }
 
 // grid (nt, batch), block ColCfg<NY>::THREADS.
-template <int NY, int MODE, int SPLIT = 1, int UNIT = 0>
-__global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLIT>::WAVES_PER_EU)) k_col(ColArgs p) {
-    using Cfg = ColCfg<NY, SPLIT>;
+template <int NY, int MODE, int SPLIT = 1, int UNIT = 0, int YS = 0>
+__global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, SPLIT, YS>::WAVES_PER_EU)) k_col(ColArgs p) {
+    using Cfg = ColCfg<NY, SPLIT, YS>;
+    static_assert(YS == 0 || (MODE == COL_PSD_AC && SPLIT == 1), "parity tiles: fused PSD + autocorrelation pass only");
+    constexpr int NYF = YS ? 2 * NY : NY;   // rows of the frame (YS: this workgroup transforms every second ky of them)
     using G = typename Cfg::G;
     constexpr int T = G::T, E = E16, NC = Cfg::NC, CPT = Cfg::CPT, CT = Cfg::CT;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
@@ -321,6 +350,9 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
         fr = blockIdx.y;
     }
     const int ct = slot / SPLIT;
+    // YS: slots [0, nt/2) are the even-ky tiles of the frame, [nt/2, nt) the odd-ky ones ([parity][ct] is the tile order in memory)
+    const int par = (YS && ct >= nt / 2) ? 1 : 0;
+    const int ctx = YS ? ct - par * (nt / 2) : ct;   // column tile
     const int cpm = cp + CPT * (slot % SPLIT);   // lane position across the memory tile
     const size_t frame = fr;
     const int nx = p.nx;
@@ -358,7 +390,7 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
     Fft3<G, 1>::template run_sets<NC, Cfg::SERIAL, MODE != COL_PSD_AC, Cfg::SB>(v, u, cp, lds, p.tw);
     B4D_STAMP(2);
     // v[c][j] = F[ky = u + T j][kx0 + c]   (COL_PSD_AC: after the stage-3 butterflies done below)
-    const int kx0 = ct * CT + NC * cpm;
+    const int kx0 = ctx * CT + NC * cpm;
 
     if (MODE == COL_FORWARD) {  // keep the 2-D half spectrum in the tile
         // laundered offset: otherwise the 16 store addresses (= the load addresses) stay live in 32 registers across the
@@ -381,7 +413,7 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
     // The last forward butterflies are interleaved with the |F|^2 epilogue (register pressure), and the
     // row index is laundered so that the 32 store offsets are not precomputed at kernel entry.
     const float s = p.psd_scale;
-    float* psd = p.psd ? p.psd + frame * (size_t)NY * nx : nullptr;
+    float* psd = p.psd ? p.psd + frame * (size_t)NYF * nx : nullptr;
     int uu = u;
     asm volatile("" : "+v"(uu));
     float2 w[NC / 2][E];
@@ -393,13 +425,13 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
 #pragma unroll
         for (int q = 0; q < G::R3; ++q) {
             const int j = a + B3 * q;
-            const int ky = uu + T * j;
+            const int ky = YS ? 2 * (uu + T * j) + par : uu + T * j;   // row of the frame's spectrum
             float pw[NC];
 #pragma unroll
             for (int k = 0; k < NC; ++k) pw[k] = v[k][j].x * v[k][j].x + v[k][j].y * v[k][j].y;
 #ifdef B4D_EXP_PSD_TILED
             if (psd) {   // timing-only: same bytes, tile-contiguous addresses (DRAM page locality experiment)
-                float* pt = psd + ((size_t)ct * NY + ky) * 32 + NC * cpm;
+                float* pt = psd + ((size_t)ctx * NYF + ky) * 32 + NC * cpm;
                 *reinterpret_cast<float2*>(pt) = make_float2(pw[0] * s, pw[1] * s);
                 *reinterpret_cast<float2*>(pt + 16) = make_float2(pw[1] * s, pw[0] * s);
             }
@@ -407,7 +439,7 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
 #else
             if (psd) {
 #endif
-                const unsigned rd = (unsigned)((ky + NY / 2) & (NY - 1)) * nx, rm = (unsigned)((NY / 2 - ky) & (NY - 1)) * nx;
+                const unsigned rd = (unsigned)((ky + NYF / 2) & (NYF - 1)) * nx, rm = (unsigned)((NYF / 2 - ky) & (NYF - 1)) * nx;
                 if (NC == 4)
                     *reinterpret_cast<float4*>(&psd[rd + nx / 2 + kx0]) =
                         make_float4(pw[0] * s, pw[1] * s, pw[2 % NC] * s, pw[3 % NC] * s);
@@ -451,7 +483,7 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
     B4D_STAMP(3);
     B4D_DRAIN();
     B4D_STAMP(4);
-    if (kx0 == 0 && uu == 0 && (p.flags & B4D_REMOVE_MEAN)) w[0][0].y = 0.f;  // DC bin: ky = 0 <-> u = 0, j = 0
+    if (kx0 == 0 && uu == 0 && par == 0 && (p.flags & B4D_REMOVE_MEAN)) w[0][0].y = 0.f;  // DC bin: ky = 0 <-> u = 0, j = 0
     // The lane position is derived AGAIN from the (laundered) thread index: otherwise the compiler keeps the load addresses and
     // the ~40 twiddle / LDS byte offsets of the forward pass alive, or u, cp and the tile offset in three registers where one
     // does -- at the 128-register cap one spilled dword reloaded here would be a scratch load, i.e. a vmcnt(0) that drains
@@ -492,7 +524,8 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT>::THREADS), (ColCfg<NY, SPLI
         // streaming (non-temporal) stores: the tile is read once more, by the row pass, after a gigabyte of other traffic -- kept
         // out of L2 it leaves the cache to the PSD half lines that do meet there (-3 % on this kernel; the PSD stores themselves
         // must stay cached: non-temporal they doubled the kernel)
-        if (!p.half_rows || u2 + T * j <= NY / 2 + 1) {
+        // rows the row pass reads: pairs (2q, 2q + 1) up to 2q = NY/2; YS: rows 0 .. NY/2 of both parity tiles
+        if (!p.half_rows || u2 + T * j <= (YS ? NY / 2 : NY / 2 + 1)) {
             static_assert(NC == 2, "one 16-byte store per row");
             __builtin_nontemporal_store(f32x4{c[0].x, c[0].y, c[1].x, c[1].y},
                                         (f32x4 B4D_GLOBAL*)at_bytes<f32x2>(sgpr_base(tile + (size_t)(T * j * CT)), toff2 * 8u));
@@ -610,6 +643,7 @@ struct RowOutArgs {
     int nblk;            // C2R_ROWS: partials per frame
     const unsigned* gate;   // C2R_MAG, optional: skip frame f when gate[f * gate_stride] != 0 (pairs that need no full map)
     int gate_stride;
+    const float2* tw_y;     // YS kernels: ny-point twiddles (the last radix-2 stage of the inverse column transform)
 };
 
 enum RowOutMode { C2R_OUT = 0, C2R_PEAK = 1, C2R_MAG = 2, C2R_ROWS = 3 };
@@ -618,8 +652,13 @@ enum RowOutMode { C2R_OUT = 0, C2R_PEAK = 1, C2R_MAG = 2, C2R_ROWS = 3 };
 //   C2R_OUT   shifted real output, scaled (flags & NORM_PEAK: by 1/peak[frame], zero lag forced to 1)
 //   C2R_PEAK  only the zero-lag value of each frame -> peak[frame]
 //   C2R_MAG   |value| * scale (signal/tracking.py:283-285) + per-workgroup arg-max partials
-template <int NX, int SEQ, int MODE, int UNIT = 0>
+// YS ("ysplit" route, C2R_OUT / C2R_PEAK, always the half form): g holds the h-point inverse transforms E (even ky) and O (odd ky)
+// of the power columns, rows 0 .. h/2 of each parity tile, h = ny/2.  Transform y combines row y of both:
+// t = conj(w^y) O, G(y) = E + t, G(h - y) = conj(E - t), and packs THESE two rows; rows y, h - y and their point mirrors
+// -y, h + y are written, every row of the map once.
+template <int NX, int SEQ, int MODE, int UNIT = 0, bool YS = false>
 __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
+    static_assert(!YS || MODE == C2R_OUT || MODE == C2R_PEAK, "ysplit: autocorrelation output only");
     using G = RowGeom<NX>;
     constexpr int T = G::T, E = E16;
     constexpr bool WV = T <= 64;   // the transform's own exchanges are wave-local; the reductions ACROSS transforms below keep s_barrier
@@ -658,13 +697,33 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
     const int pair = MODE == C2R_PEAK   ? 0
                      : MODE == C2R_ROWS ? (peak_pair + ny / 2 - 1 + min(bx * SEQ + seq, 2)) % (ny / 2)
                                         : bx * SEQ + seq;
-    const bool live = (MODE == C2R_OUT && p.half) ? 2 * pair <= ny / 2 : 2 * pair < ny;
-    const int yl = live ? 2 * pair : 0;
+    const bool live = YS ? 4 * pair <= ny : (MODE == C2R_OUT && p.half) ? 2 * pair <= ny / 2 : 2 * pair < ny;
+    const int yl = live ? (YS ? pair : 2 * pair) : 0;
     float2* lds = lds_all + seq * G::LDS_ELEMS;
     float2 v[E];
+    float2 wc = make_float2(1.f, 0.f);
+    if (YS) {   // conj(w^y), uniform per transform
+        wc = p.tw_y[yl];
+        wc.y = -wc.y;
+    }
 #pragma unroll
     for (int j = 0; j < E / 2; ++j) {
         const int k = u + T * j;
+        if (YS) {
+            const size_t o = spec_index(2 * frame, nt, ny / 2, ct_w, yl, k);
+            const f32x2 e_ = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(p.g + o)),
+                        o_ = __builtin_nontemporal_load(reinterpret_cast<const f32x2*>(p.g + o + (size_t)(ny / 2) * (NX / 2)));
+            const float2 ev = make_float2(e_.x, e_.y), t = cmul(make_float2(o_.x, o_.y), wc);
+            const float2 a = cadd(ev, t), d = csub(ev, t), b = make_float2(d.x, -d.y);
+            if (k == 0) {  // DC and Nyquist bins of both rows are real
+                v[j] = make_float2(b.x, a.x);
+                lds[NX / 2] = make_float2(p.gnyq[frame * ny + ny / 2 - yl], p.gnyq[frame * ny + yl]);
+            } else {
+                v[j] = make_float2(a.y + b.x, a.x - b.y);        // swap(A + iB)
+                lds[NX - k] = make_float2(b.x - a.y, a.x + b.y);  // swap(conj A + i conj B)
+            }
+            continue;
+        }
         // C2R_MAG (issue-bound, profiles/r03_pmc_cfg3_sq.txt): the tile index without the integer division by the run-time tile width
         // (a power of two) and with a 24-bit multiply -- the generic form costs ~40 quarter-rate multiplies per lane here.  The cfg2
         // instantiation keeps spec_index: there the same change cost K3 1 % (instruction order).
@@ -691,8 +750,9 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
         if (threadIdx.x == 0) p.peak[frame] = v[0].y;
         return;
     }
-    const int y0 = 2 * pair;
-    const int ra = (y0 + ny / 2) & (ny - 1), rb = (y0 + 1 + ny / 2) & (ny - 1);
+    const int y0 = YS ? pair : 2 * pair;        // rows of the (unshifted) map in Re z and Im z: y0 and y0 + 1, YS: y0 and ny/2 - y0
+    const int y1 = YS ? ny / 2 - pair : y0 + 1;
+    const int ra = (y0 + ny / 2) & (ny - 1), rb = (y1 + ny / 2) & (ny - 1);
     float* o0 = p.out + (frame * ny + ra) * (size_t)NX;
     float* o1 = p.out + (frame * ny + rb) * (size_t)NX;
     if (MODE == C2R_OUT) {
@@ -706,10 +766,11 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
             s = unit_peak ? 1.0f / pk : p.scale;
         }
         // half mode: rows 0..ny/2 are written directly, rows 1..ny/2-1 also as their point mirrors
-        const bool wr1 = !p.half || y0 + 1 <= ny / 2;
-        const bool mir0 = p.half && y0 >= 1 && y0 < ny / 2, mir1 = p.half && y0 + 1 < ny / 2;
+        // YS: y0 = 0 writes rows 0 and ny/2 (their own mirrors), y0 = ny/4 holds the same row twice (written once, with its mirror)
+        const bool wr1 = YS ? 4 * y0 < ny : !p.half || y0 + 1 <= ny / 2;
+        const bool mir0 = YS ? y0 >= 1 : p.half && y0 >= 1 && y0 < ny / 2, mir1 = YS ? y0 >= 1 && 4 * y0 < ny : p.half && y0 + 1 < ny / 2;
         float* q0 = p.out + (frame * ny + ((ny / 2 - y0) & (ny - 1))) * (size_t)NX;
-        float* q1 = p.out + (frame * ny + ((ny / 2 - y0 - 1) & (ny - 1))) * (size_t)NX;
+        float* q1 = p.out + (frame * ny + ((ny / 2 - y1) & (ny - 1))) * (size_t)NX;
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             const int x = u + T * j, c = (x + NX / 2) & (NX - 1), cm = (NX / 2 - x) & (NX - 1);
@@ -859,6 +920,7 @@ struct b4d_plan {
     int ny, nx, chunk, ct_w;
     float2* tw_x = nullptr;    // nx-point twiddles
     float2* tw_y = nullptr;    // ny-point twiddles
+    float2* tw_yh = nullptr;   // ny/2-point twiddles (ny = 2048: the parity-tile column pass of the "ysplit" route)
     float2* spec = nullptr;    // chunk * ny * nx/2
     float* nyq_rows = nullptr; // chunk * ny: Nyquist bins after the row pass
     float* gnyq = nullptr;     // chunk * ny: Nyquist column after the inverse column pass
@@ -981,6 +1043,20 @@ static int launch_col(const ColArgs& a, int ntiles, int batch, hipStream_t st) {
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
+// "ysplit" route (ny = 2048): 1024-point parity tiles, a.tw / a.tw_inv = 1024-point twiddles; grid (2 nt', batch)
+template <int YS = 1>
+static int launch_col_ys(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {
+    using Cfg = ColCfg<1024, 1, YS>;
+    if (pl->ny != 2048 || (pl->nx / 2) % Cfg::CT) return fail(B4D_ESIZE, "ysplit column pass: unsupported size");
+    {
+        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<1024, COL_PSD_AC, 1, B4D_UNIT_TAG, YS>), Cfg::LDS_BYTES);
+        if (rc_lds) return rc_lds;
+    }
+    hipLaunchKernelGGL((k_col<1024, COL_PSD_AC, 1, B4D_UNIT_TAG, YS>), dim3(2 * ((pl->nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
+                       Cfg::LDS_BYTES, st, a);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
 template <int MODE>
 static int dispatch_col(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {
     const int ntiles = (pl->nx / 2) / pl->ct_w;
@@ -1020,12 +1096,30 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
     const dim3 block((NX / E16) * SEQ);
     if (srcs)
         hipLaunchKernelGGL((k_row_r2c<NX, SEQ, true>), dim3((pl->ny / 2 + SEQ - 1) / SEQ, batch), block, 0, st, in, spec, nyq_rows,
-                           pl->tw_x, pl->ny, pl->ct_w, srcs);
+                           pl->tw_x, pl->ny, pl->ct_w, srcs, (const float2*)nullptr);
     else
         hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER>), dim3((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch), block, 0, st,
-                           in, spec, nyq_rows, pl->tw_x, pl->ny, pl->ct_w, srcs);
+                           in, spec, nyq_rows, pl->tw_x, pl->ny, pl->ct_w, srcs, (const float2*)nullptr);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
+}
+// "ysplit" route: rows p and p + ny/2 per transform, parity tile sets of ct_w columns (a template so that only the unit that
+// calls it instantiates the kernels)
+template <int NX>
+static int launch_r2c_ys(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, int ct_w, int batch, hipStream_t st) {
+    constexpr int SEQ = row_seq(NX);
+    constexpr int ITER = NX >= 1024 ? B4D_K1_ITER : 1;
+    hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true>), dim3((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch),
+                       dim3((NX / E16) * SEQ), 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, (const RowSrc*)nullptr, pl->tw_y);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+template <int DUMMY = 0>
+static int dispatch_r2c_ys(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows, int ct_w) {
+#define B4D_CALL(N) launch_r2c_ys<N>(pl, in, spec, nyq_rows, ct_w, batch, st)
+    B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
+#undef B4D_CALL
+    return fail(B4D_ESIZE, "unsupported nx");
 }
 // rows -> half spectra into `spec` / `nyq_rows` (default: the plan's chunk workspace); srcs != null selects
 // ROI / z-score sources
@@ -1076,6 +1170,33 @@ static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mo
     hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG>), grid, block, 0, st, a);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
+}
+// "ysplit" route: C2R_OUT on the parity tiles (a.ct_w, a.tw_y), with the same zero-lag pre-pass when NORM_PEAK
+template <int NX>
+static int launch_c2r_ys(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev) {
+    constexpr int SEQ = row_seq(NX);
+    const dim3 grid((pl->ny / 4 + 1 + SEQ - 1) / SEQ, batch), block((NX / E16) * SEQ);
+    if (batch < 1) return B4D_OK;
+    if (a.flags & B4D_NORM_PEAK) {
+        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_PEAK, B4D_UNIT_TAG, true>), dim3(1, batch), block, 0, st, a);
+        B4D_HIP(hipGetLastError());
+        if (ev) {
+            hipEvent_t e;
+            B4D_HIP(hipEventCreate(&e));
+            ev->push_back(e);
+            B4D_HIP(hipEventRecord(e, st));
+        }
+    }
+    hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, true>), grid, block, 0, st, a);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+template <int DUMMY = 0>
+static int dispatch_c2r_ys(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev) {
+#define B4D_CALL(N) launch_c2r_ys<N>(pl, a, batch, st, ev)
+    B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
+#undef B4D_CALL
+    return fail(B4D_ESIZE, "unsupported nx");
 }
 static int dispatch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, int mode = C2R_OUT,
                         std::vector<hipEvent_t>* ev = nullptr, int* nblk = nullptr) {

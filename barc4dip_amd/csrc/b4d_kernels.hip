@@ -57,6 +57,7 @@ int lane_stream(int idx, hipStream_t* out) {
 std::atomic<int> g_opt_track_predict{1};
 std::atomic<int> g_opt_lanes{1};
 std::atomic<int> g_opt_exp{0};
+std::atomic<int> g_opt_ysplit{1};   // "ysplit": 2048-row PSD + autocorrelation through parity tiles (b4d_fft2d.hpp); 0 = full-column tiles
 // b4d_spectrum.hip
 int spectrum_rows_last(const b4d_plan* pl, float2* spec, const float* frames, int batch, float2* out, hipStream_t st);
 }  // namespace b4d
@@ -114,7 +115,8 @@ int b4d_set_option(const char* name, int value) {
         std::atomic<int>* v;
         int lo, hi;
     };
-    const Opt opts[] = {{"track_predict_bin", &g_opt_track_predict, 0, 2}, {"lanes", &g_opt_lanes, 0, 1}, {"exp", &g_opt_exp, 0, 255}};
+    const Opt opts[] = {{"track_predict_bin", &g_opt_track_predict, 0, 2}, {"lanes", &g_opt_lanes, 0, 1}, {"exp", &g_opt_exp, 0, 255},
+                        {"ysplit", &g_opt_ysplit, 0, 1}};
     for (const Opt& o : opts)
         if (!strcmp(name, o.name)) {
             if (value < o.lo || value > o.hi)
@@ -192,6 +194,7 @@ static int plan_create_impl(int ny, int nx, int chunk, bool force_general, b4d_p
     p->ct_w = col_ct(ny);
     int rc = make_twiddles(nx, &p->tw_x);
     if (rc == B4D_OK) rc = make_twiddles(ny, &p->tw_y);
+    if (rc == B4D_OK && ny == 2048) rc = make_twiddles(ny / 2, &p->tw_yh);
     if (rc != B4D_OK) {
         b4d_plan_destroy(p);
         return rc;
@@ -213,6 +216,7 @@ int b4d_plan_destroy(b4d_plan* p) {
     if (!p) return B4D_OK;
     if (p->tw_x) (void)hipFree(p->tw_x);
     if (p->tw_y) (void)hipFree(p->tw_y);
+    if (p->tw_yh) (void)hipFree(p->tw_yh);
     if (p->spec) (void)hipFree(p->spec);
     if (p->peak) (void)hipFree(p->peak);
     if (p->nyq_rows) (void)hipFree(p->nyq_rows);
@@ -246,6 +250,10 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
     if (!psd && !autocorr) return fail(B4D_EINVAL, "both outputs are null");
     if (pl->general) return general_psd_autocorr(pl, frames, batch, psd, psd_scale, autocorr, flags, st);
     const size_t fpix = (size_t)pl->ny * pl->nx;
+    // one route per call, chosen by the frame shape alone (never by batch, chunk or lanes): 2048-row frames take the parity-tile
+    // route, where the row passes do one radix-2 stage of the column transform
+    const int ysplit = (pl->ny == 2048 && pl->tw_yh) ? g_opt_ysplit.load() : 0;
+    constexpr int ys_ct = ColCfg<1024, 1, 1>::CT;   // columns per parity tile
     std::vector<hipEvent_t> ev;
     auto mark = [&]() -> int {
         if (!kernel_ms) return B4D_OK;
@@ -272,13 +280,15 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
         float* nyq_rows = pl->nyq_rows + (size_t)pl->ny * so;
         float* gnyq = pl->gnyq + (size_t)pl->ny * so;
         if ((rc = mark())) break;
-        if ((rc = dispatch_r2c(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows))) break;
+        if ((rc = ysplit ? dispatch_r2c_ys(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows, ys_ct)
+                         : dispatch_r2c(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows)))
+            break;
         if ((rc = mark())) break;
         ColArgs ca{};
         ca.spec = spec;
         ca.psd = psd ? psd + b0 * fpix : nullptr;
-        ca.tw = pl->tw_y;
-        ca.tw_inv = pl->tw_y;
+        ca.tw = ysplit ? pl->tw_yh : pl->tw_y;
+        ca.tw_inv = ca.tw;
         ca.psd_scale = psd_scale;
         ca.nx = pl->nx;
         ca.flags = flags;
@@ -286,7 +296,7 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
 #ifdef B4D_DIAG
         ca.diag = g_diag;
 #endif
-        if ((rc = col_psd_ac_pass(pl, ca, nb, ls))) break;
+        if ((rc = col_psd_ac_pass(pl, ca, nb, ls, ysplit))) break;
         NyqArgs na{};
         na.rows = nyq_rows;
         na.g_out = gnyq;
@@ -303,10 +313,11 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
             ra.tw = pl->tw_x;
             ra.scale = 1.0f / ((float)pl->nx * (float)pl->ny);
             ra.ny = pl->ny;
-            ra.ct_w = pl->ct_w;
+            ra.ct_w = ysplit ? ys_ct : pl->ct_w;
+            ra.tw_y = pl->tw_y;
             ra.flags = flags;
             ra.half = 1;
-            if ((rc = row_out_pass(pl, ra, nb, ls, kernel_ms ? &ev : nullptr))) break;
+            if ((rc = row_out_pass(pl, ra, nb, ls, kernel_ms ? &ev : nullptr, ysplit))) break;
         }
         if ((rc = mark())) break;
     }

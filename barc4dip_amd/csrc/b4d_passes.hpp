@@ -5,13 +5,15 @@
 //   b4d_rowout.hip   k_row_c2r<.., C2R_OUT> (and its C2R_PEAK pre-pass)  max-ILP strategy (-amdgpu-sched-strategy=max-ilp):
 //                    134 VGPRs, three waves per SIMD instead of four, K3 -3 ... -4 %
 // Either flag on the whole of b4d_kernels.hip costs the other kernels what it wins (max-ILP: K1 +1 %, K2 +0.5 %; both together
-// spill in k_col).  Outputs are bit-identical to the default scheduler's.
+// spill in k_col).  Outputs are bit-identical to the default scheduler's.  The kernels of the "ysplit" route of 2048-row frames
+// (k_col<1024, .., YS> on parity tiles, k_row_c2r<.., YS>) are instantiated in the same two units, with the same flags.
 #pragma once
 #include <vector>
 
 #include "b4d_fft2d.hpp"
 
 namespace b4d {
-int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st);
-int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev);
+// ysplit: 0 = tiles of all ny rows; 1 = the "ysplit" route of 2048-row frames (parity tiles, b4d_fft2d.hpp)
+int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, int ysplit);
+int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, int ysplit);
 }  // namespace b4d

@@ -53,6 +53,11 @@ const char* b4d_last_error(void);
  *                        caller's stream and ONE library-owned stream per device, forked from and joined into the caller's stream
  *                        by events inside the call (stream order as seen by the caller is unchanged); 0 = everything on the
  *                        caller's stream alone (for callers that must not see a second stream).
+ *   "ysplit"             0 / 1 (default 1): 1 = PSD / autocorrelation of 2048-row frames (power-of-two plans) move one radix-2
+ *                        stage of the column transform into the row passes, so that the column pass works on 32-column tiles of
+ *                        every second spectrum row and stores whole 128-byte PSD lines; 0 = 16-column tiles of all rows.  The
+ *                        route depends on the frame shape alone (results of a stack equal those of its frames, bit for bit); the
+ *                        two routes split the column transform differently and agree to float32 rounding, not bit for bit.
  *   "exp"                0 .. 255 (default 0): development switch for A/B runs of kernel variants under test in ONE process
  *                        (tools/dev_*.py); a shipped library has no reader of it.
  * Values outside an option's range and unknown names return B4D_EINVAL; the options are atomics, read once per entry-point call. */

@@ -29,9 +29,11 @@ def main():
     alg = {"k_col": (4 * n * n + 4 * n * n + 8 * (n // 2 + 2) * (n // 2)) * frames, "k_row_r2c": 8 * n * n * frames,
            "k_row_c2r": (4 * (n // 2 + 2) * n + 4 * n * n) * frames}
     res = {}
-    for tag, match in (("k_col", "k_col<2048, 0"), ("k_row_r2c", "k_row_r2c<2048"), ("k_row_c2r", "k_row_c2r<2048, 2, 0")):
-        f = [v for k, v in fe.items() if match in k]
-        w = [v for k, v in wr.items() if match in k]
+    # the column pass of 2048-row frames is k_col<1024, 0, 1, 1, 1> on the "ysplit" route, k_col<2048, 0, ...> otherwise
+    for tag, match in (("k_col", ("k_col<1024, 0, 1, 1, 1>", "k_col<2048, 0")), ("k_row_r2c", ("k_row_r2c<2048",)),
+                       ("k_row_c2r", ("k_row_c2r<2048, 2, 0",))):
+        f = [v for k, v in fe.items() if any(m in k for m in match)]
+        w = [v for k, v in wr.items() if any(m in k for m in match)]
         if not f or not w:
             continue
         res[tag] = {"FETCH_SIZE_KB_raw": f[0], "WRITE_SIZE_KB": w[0], "hbm_bytes_per_launch": (2 * f[0] + w[0]) * 1024,
