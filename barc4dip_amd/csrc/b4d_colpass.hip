@@ -5,8 +5,9 @@
 #include "b4d_passes.hpp"
 
 namespace b4d {
-int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, int ysplit) {
-    if (ysplit) return launch_col_ys(pl, a, batch, st);
-    return dispatch_col<COL_PSD_AC>(pl, a, batch, st);
+int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, const Route& rt) {
+    if (!rt.parity) return dispatch_col<COL_PSD_AC>(pl, a, batch, st);
+    if (pl->ny != 2048) return fail(B4D_ESIZE, "parity-tile column pass: 2048-row frames only");
+    return launch_col<1024, COL_PSD_AC, 1>(a, batch, st);
 }
 }  // namespace b4d

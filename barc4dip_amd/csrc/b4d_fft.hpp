@@ -357,58 +357,25 @@ struct Fft3 {
     }
 
     // NS register sets that share lane geometry go through the exchange buffer one after the other.
-    // Same entry/exit contract as run().  SERIAL pins the per-set order with sched_barriers (only
-    // useful when the kernel sits at its VGPR cap); otherwise the compiler may overlap set s+1's
-    // butterflies with set s's LDS round trip.
-    // SB > 1: SB sets go through the buffer TOGETHER (the buffer holds SB regions of SET_ELEMS complex
-    // values): half the barriers and twice the independent work between them.
-    template <int NS, bool SERIAL, bool WITH_STAGE3 = true, int SB = 1>
+    // Same entry/exit contract as run().  The per-set order is pinned with sched_barriers: every caller
+    // sits at its VGPR cap, where the compiler must not overlap set s+1's butterflies with set s's LDS
+    // round trip.
+    template <int NS, bool WITH_STAGE3 = true>
     static __device__ __forceinline__ void run_sets(float2 (&v)[NS][E], int u, int ci, float2* __restrict__ lds,
                                                     const float2* __restrict__ tw) {
-        if (SB > 1) {
-            static_assert(NS % SB == 0, "batch must divide the set count");
-            constexpr int SET_ELEMS = G::LDS_ELEMS * CI;
-#pragma unroll
-            for (int b = 0; b < NS; b += SB) {
-#pragma unroll
-                for (int s = 0; s < SB; ++s) stage1(v[b + s], u, tw);
-                if (b > 0) sync();
-#pragma unroll
-                for (int s = 0; s < SB; ++s) xchg1_write(v[b + s], u, ci, lds + s * SET_ELEMS);
-                sync();
-#pragma unroll
-                for (int s = 0; s < SB; ++s) xchg1_read(v[b + s], u, ci, lds + s * SET_ELEMS);
-            }
-#pragma unroll
-            for (int b = 0; b < NS; b += SB) {
-#pragma unroll
-                for (int s = 0; s < SB; ++s) stage2(v[b + s], u, tw);
-                sync();
-#pragma unroll
-                for (int s = 0; s < SB; ++s) xchg2_write(v[b + s], u, ci, lds + s * SET_ELEMS);
-                sync();
-#pragma unroll
-                for (int s = 0; s < SB; ++s) xchg2_read(v[b + s], u, ci, lds + s * SET_ELEMS);
-            }
-            if (WITH_STAGE3) {
-#pragma unroll
-                for (int s = 0; s < NS; ++s) stage3(v[s]);
-            }
-            return;
-        }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             stage1(v[s], u, tw);
             if (s > 0) sync();
             xchg1(v[s], u, ci, lds);
-            if (SERIAL) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             stage2(v[s], u, tw);
             sync();
             xchg2(v[s], u, ci, lds);
-            if (SERIAL) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
         }
         if (WITH_STAGE3) {
 #pragma unroll

@@ -264,28 +264,19 @@ struct ColArgs {
 //               measured 1.23x faster than 512 lanes x 4 columns at 2 waves per SIMD)
 //   NY == 4096: CPT = 4 -> CT = 8 (a 16-column tile would need the whole register file)
 // __launch_bounds__(THREADS, 4) caps every variant at 128 VGPRs so that smaller NY run several workgroups per CU.
-// SPLIT workgroups share one memory tile (each takes CT / SPLIT adjacent columns of it): the layout keeps whole
-// 128-B lines per row while two 512-lane workgroups fit one CU and overlap each other's memory and butterfly phases.
 // YS ("ysplit" route of 2048-row frames, NY = 1024 here): the row passes do one radix-2 stage of the column transform, a
 // workgroup owns one PARITY tile (the even or the odd ky of CT columns): CPT = 16 -> CT = 32 columns x 1024 rows, the same
 // 256 KiB in 1024 lanes, whole 128-B lines in every direct PSD store.  (16-column parity tiles, 512 lanes and two workgroups
 // per CU, were measured 20 % slower on the column pass: DESIGN.md §8.1.)
-template <int NY, int SPLIT = 1, int YS = 0>
+template <int NY, int YS = 0>
 struct ColCfg {
     static constexpr int NC = 2;
-    static constexpr int CPT = (NY == 4096 ? 4 : 8) / SPLIT * (YS ? 2 : 1);
-    static constexpr int CT = NC * CPT * SPLIT;   // columns per MEMORY tile
+    static constexpr int CPT = (NY == 4096 ? 4 : 8) * (YS ? 2 : 1);
+    static constexpr int CT = NC * CPT;   // columns per tile
     static constexpr int THREADS = CPT * (NY / E16);
     static constexpr int WAVES_PER_EU = THREADS >= 256 ? 4 : 1;
     using G = ColGeom<NY, CPT>;
-    static constexpr int SB = 1;  // sets per LDS round trip (one exchange region = 132 KiB at NY = 2048)
-    static constexpr size_t LDS_BYTES = sizeof(float2) * (size_t)G::LDS_ELEMS * CPT * SB;
-    static constexpr bool SERIAL = true;  // at the 128-VGPR cap: pin the per-set order
-};
-
-// 4-byte-aligned 16-byte store (gfx950 runs in unaligned access mode: one global_store_dwordx4)
-struct __attribute__((packed, aligned(4))) float4_u {
-    float x, y, z, w;
+    static constexpr size_t LDS_BYTES = sizeof(float2) * (size_t)G::LDS_ELEMS * CPT;   // one exchange region (132 KiB at NY = 2048)
 };
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));   // plain vector values for accesses through address-space pointers
@@ -311,12 +302,6 @@ __device__ __forceinline__ V* sgpr_base(V* p) {
 }
 
 template <int NC>
-__device__ __forceinline__ void store_cols(f32x2 B4D_GLOBAL* rowp, const float2 (&c)[NC]) {
-#pragma unroll
-    for (int h = 0; h < NC / 2; ++h)
-        *(f32x4 B4D_GLOBAL*)(rowp + 2 * h) = f32x4{c[2 * h].x, c[2 * h].y, c[2 * h + 1].x, c[2 * h + 1].y};
-}
-template <int NC>
 __device__ __forceinline__ void store_cols(float2* __restrict__ rowp, const float2 (&c)[NC]) {
 #pragma unroll
     for (int h = 0; h < NC / 2; ++h)
@@ -324,44 +309,41 @@ __device__ __forceinline__ void store_cols(float2* __restrict__ rowp, const floa
 }
 
 // grid (nt, batch), block ColCfg<NY>::THREADS.
-template <int NY, int MODE, int SPLIT = 1, int UNIT = 0, int YS = 0>
-__global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, SPLIT, YS>::WAVES_PER_EU)) k_col(ColArgs p) {
-    using Cfg = ColCfg<NY, SPLIT, YS>;
-    static_assert(YS == 0 || (MODE == COL_PSD_AC && SPLIT == 1), "parity tiles: fused PSD + autocorrelation pass only");
+template <int NY, int MODE, int UNIT = 0, int YS = 0>
+__global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WAVES_PER_EU)) k_col(ColArgs p) {
+    using Cfg = ColCfg<NY, YS>;
+    static_assert(YS == 0 || MODE == COL_PSD_AC, "parity tiles: fused PSD + autocorrelation pass only");
+    static_assert(Cfg::NC == 2, "two columns per lane: one 16-byte load / store per row, one 8-byte PSD store");
     constexpr int NYF = YS ? 2 * NY : NY;   // rows of the frame (YS: this workgroup transforms every second ky of them)
     using G = typename Cfg::G;
     constexpr int T = G::T, E = E16, NC = Cfg::NC, CPT = Cfg::CPT, CT = Cfg::CT;
     extern __shared__ __attribute__((aligned(16))) float2 lds[];
     const int cp = threadIdx.x % CPT, u = threadIdx.x / CPT;
-    const int nt = gridDim.x / SPLIT;
+    const int nt = gridDim.x;
     // Workgroups are dealt round-robin over the 8 XCDs (linear workgroup id % 8).  Neighbouring column tiles write
     // the two 64-B halves of every 128-B PSD line and share the 64-B sectors of the Hermitian-mirror stores (the
     // mirror of 16 aligned columns is misaligned by one float): those merge only in a common L2.  With batch % 8 == 0
     // every tile of frame f runs on XCD f % 8 (measured -6% on the 2048^2 kernel against per-XCD tile ranges, which
     // leave one tile boundary in eight split across two L2s); otherwise each XCD takes a contiguous tile range.
-    // Speed only: any placement is correct.  The SPLIT parts of a tile are consecutive workgroups of one XCD.
-    int slot, fr;
+    // Speed only: any placement is correct.
+    int ct, fr;
     if (gridDim.y % 8 == 0) {
         const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y, k = lin / 8;
         fr = 8 * (k / gridDim.x) + lin % 8;
-        slot = k % gridDim.x;
+        ct = k % gridDim.x;
     } else {
-        slot = (nt % 8 == 0) ? (blockIdx.x % 8) * (nt * SPLIT / 8) + blockIdx.x / 8 : blockIdx.x;
+        ct = (nt % 8 == 0) ? (blockIdx.x % 8) * (nt / 8) + blockIdx.x / 8 : blockIdx.x;
         fr = blockIdx.y;
     }
-    const int ct = slot / SPLIT;
     // YS: slots [0, nt/2) are the even-ky tiles of the frame, [nt/2, nt) the odd-ky ones ([parity][ct] is the tile order in memory)
     const int par = (YS && ct >= nt / 2) ? 1 : 0;
     const int ctx = YS ? ct - par * (nt / 2) : ct;   // column tile
-    const int cpm = cp + CPT * (slot % SPLIT);   // lane position across the memory tile
     const size_t frame = fr;
     const int nx = p.nx;
     float2* tile = p.spec + ((frame * nt + ct) * (size_t)NY) * CT;
-    const unsigned toff = (unsigned)u * CT + NC * cpm;  // element offset of (row u, first column of this lane)
+    const unsigned toff = (unsigned)u * CT + NC * cp;  // element offset of (row u, first column of this lane)
     float2 v[NC][E];
     B4D_STAMP(0);
-    // column pairs in issue order: the first pair's loads complete first, so its butterflies start while the
-    // second pair is still streaming in (loads return in order; the compiler's counted vmcnt does the rest)
     int ry0 = 0, ry1 = NY;
     if (MODE == COL_FORWARD && p.srcs) {
         ry0 = p.srcs[fr].y0;
@@ -374,7 +356,7 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, 
             if (MODE == COL_FORWARD) {   // clamped row + select: the load stays unconditional (no branch per load), rows outside the
                                          // ROI re-read a ROI row that other lanes fetch anyway
                 const int ky = u + T * j, kc = min(max(ky, ry0), ry1 - 1);
-                float4 q = *reinterpret_cast<const float4*>(tile + (size_t)kc * CT + NC * cpm + 2 * h);
+                float4 q = *reinterpret_cast<const float4*>(tile + (size_t)kc * CT + NC * cp + 2 * h);
                 if (ky < ry0 || ky >= ry1) q = make_float4(0.f, 0.f, 0.f, 0.f);
                 v[2 * h][j] = make_float2(q.x, q.y);
                 v[2 * h + 1][j] = make_float2(q.z, q.w);
@@ -387,10 +369,10 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, 
     }
     B4D_DRAIN();
     B4D_STAMP(1);
-    Fft3<G, 1>::template run_sets<NC, Cfg::SERIAL, MODE != COL_PSD_AC, Cfg::SB>(v, u, cp, lds, p.tw);
+    Fft3<G, 1>::template run_sets<NC, MODE != COL_PSD_AC>(v, u, cp, lds, p.tw);
     B4D_STAMP(2);
     // v[c][j] = F[ky = u + T j][kx0 + c]   (COL_PSD_AC: after the stage-3 butterflies done below)
-    const int kx0 = ctx * CT + NC * cpm;
+    const int kx0 = ctx * CT + NC * cp;
 
     if (MODE == COL_FORWARD) {  // keep the 2-D half spectrum in the tile
         // laundered offset: otherwise the 16 store addresses (= the load addresses) stay live in 32 registers across the
@@ -429,51 +411,14 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, 
             float pw[NC];
 #pragma unroll
             for (int k = 0; k < NC; ++k) pw[k] = v[k][j].x * v[k][j].x + v[k][j].y * v[k][j].y;
-#ifdef B4D_EXP_PSD_TILED
-            if (psd) {   // timing-only: same bytes, tile-contiguous addresses (DRAM page locality experiment)
-                float* pt = psd + ((size_t)ctx * NYF + ky) * 32 + NC * cpm;
-                *reinterpret_cast<float2*>(pt) = make_float2(pw[0] * s, pw[1] * s);
-                *reinterpret_cast<float2*>(pt + 16) = make_float2(pw[1] * s, pw[0] * s);
-            }
-            if (false) {
-#else
             if (psd) {
-#endif
                 const unsigned rd = (unsigned)((ky + NYF / 2) & (NYF - 1)) * nx, rm = (unsigned)((NYF / 2 - ky) & (NYF - 1)) * nx;
-                if (NC == 4)
-                    *reinterpret_cast<float4*>(&psd[rd + nx / 2 + kx0]) =
-                        make_float4(pw[0] * s, pw[1] * s, pw[2 % NC] * s, pw[3 % NC] * s);
-                else
-                    *at_bytes<f32x2>(psd, (rd + nx / 2 + kx0) * 4u) = f32x2{pw[0] * s, pw[1] * s};
-                // Hermitian mirror: columns nx/2 - kx0 - k, descending -> one reversed (4-byte aligned) vector store
-                if (NC == 4 && kx0 >= 1) {
-                    float4_u m;
-                    m.x = pw[3 % NC] * s;
-                    m.y = pw[2 % NC] * s;
-                    m.z = pw[1] * s;
-                    m.w = pw[0] * s;
-                    *reinterpret_cast<float4_u*>(&psd[rm + nx / 2 - kx0 - 3]) = m;
-                } else {
-#if defined(B4D_EXP_NOMIRROR)
-#elif defined(B4D_EXP_ALIGNED_MIRROR)
-                    *reinterpret_cast<float2*>(&psd[rm + nx / 2 - kx0 - 2]) = make_float2(pw[1] * s, pw[0] * s);
-#elif defined(B4D_PAIR_MIRROR)
-                    // columns nx/2 - kx descend as kx ascends: the 8-byte aligned pairs are (kx0 + 2, kx0 + 1), i.e. the
-                    // next lane's first column and this lane's second
-                    const float nb = __shfl_down(pw[0], 1, 64);
-                    if (cpm < CT / NC - 1)
-                        *reinterpret_cast<float2*>(&psd[rm + nx / 2 - kx0 - 2]) = make_float2(nb * s, pw[1] * s);
-                    else
-                        psd[rm + nx / 2 - kx0 - 1] = pw[1] * s;
-                    if (cpm == 0 && kx0 >= 1) psd[rm + nx / 2 - kx0] = pw[0] * s;
-#else
-                    // columns nx/2 - kx0 - 1, nx/2 - kx0 (column 0 has no mirror).  Two dword stores: ONE 8-byte store on the 4-byte
-                    // boundary (the mirror of an aligned pair starts one float off) measured +6 % on the kernel
-                    const unsigned mo = (rm + nx / 2 - kx0 - 1) * 4u;
-                    *at_bytes<float>(psd, mo) = pw[1] * s;
-                    if (kx0 >= 1) *at_bytes<float>(psd, mo + 4u) = pw[0] * s;
-#endif
-                }
+                *at_bytes<f32x2>(psd, (rd + nx / 2 + kx0) * 4u) = f32x2{pw[0] * s, pw[1] * s};
+                // Hermitian mirror: columns nx/2 - kx0 - 1, nx/2 - kx0 (column 0 has no mirror).  Two dword stores: ONE 8-byte
+                // store on the 4-byte boundary (the mirror of an aligned pair starts one float off) measured +6 % on the kernel
+                const unsigned mo = (rm + nx / 2 - kx0 - 1) * 4u;
+                *at_bytes<float>(psd, mo) = pw[1] * s;
+                if (kx0 >= 1) *at_bytes<float>(psd, mo + 4u) = pw[0] * s;
             }
             // inverse inputs, already (im, re)-swapped so that the forward code inverts: Pa + i Pb -> (Pb, Pa)
 #pragma unroll
@@ -492,25 +437,20 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, 
     int tid2 = threadIdx.x;
     asm volatile("" : "+v"(tid2));
     const int cp2 = tid2 % CPT, u2 = tid2 / CPT;
-    const unsigned toff2 = (unsigned)u2 * CT + NC * (cp2 + CPT * (slot % SPLIT));
+    const unsigned toff2 = (unsigned)u2 * CT + NC * cp2;
     __syncthreads();
-    Fft3<G, 1>::template run_sets<NC / 2, Cfg::SERIAL, true, Cfg::SB>(w, u2, cp2, lds, tw2);
+    Fft3<G, 1>::template run_sets<NC / 2>(w, u2, cp2, lds, tw2);
     B4D_STAMP(5);
-    // V[y] = Ga[y] + i Gb[y] with Ga, Gb Hermitian in y: split with V[-y], one set at a time
+    // V[y] = Ga[y] + i Gb[y] with Ga, Gb Hermitian in y: split with V[-y], one set at a time through the exchange region
     float2 vr[NC / 2][E];
-    constexpr int SETE = G::LDS_ELEMS * CPT;  // one exchange region (complex elements)
 #pragma unroll
-    for (int b = 0; b < NC / 2; b += Cfg::SB) {
+    for (int h = 0; h < NC / 2; ++h) {
         __syncthreads();
 #pragma unroll
-        for (int h = b; h < b + Cfg::SB; ++h)
-#pragma unroll
-            for (int j = 0; j < E; ++j) lds[(h - b) * SETE + (u2 + T * j) * CPT + cp2] = make_float2(w[h][j].y, w[h][j].x);
+        for (int j = 0; j < E; ++j) lds[(u2 + T * j) * CPT + cp2] = make_float2(w[h][j].y, w[h][j].x);
         __syncthreads();
 #pragma unroll
-        for (int h = b; h < b + Cfg::SB; ++h)
-#pragma unroll
-            for (int j = 0; j < E; ++j) vr[h][j] = lds[(h - b) * SETE + ((NY - (u2 + T * j)) & (NY - 1)) * CPT + cp2];
+        for (int j = 0; j < E; ++j) vr[h][j] = lds[((NY - (u2 + T * j)) & (NY - 1)) * CPT + cp2];
     }
 #pragma unroll
     for (int j = 0; j < E; ++j) {
@@ -526,7 +466,6 @@ __global__ void __launch_bounds__((ColCfg<NY, SPLIT, YS>::THREADS), (ColCfg<NY, 
         // must stay cached: non-temporal they doubled the kernel)
         // rows the row pass reads: pairs (2q, 2q + 1) up to 2q = NY/2; YS: rows 0 .. NY/2 of both parity tiles
         if (!p.half_rows || u2 + T * j <= (YS ? NY / 2 : NY / 2 + 1)) {
-            static_assert(NC == 2, "one 16-byte store per row");
             __builtin_nontemporal_store(f32x4{c[0].x, c[0].y, c[1].x, c[1].y},
                                         (f32x4 B4D_GLOBAL*)at_bytes<f32x2>(sgpr_base(tile + (size_t)(T * j * CT)), toff2 * 8u));
         }
@@ -1027,40 +966,35 @@ static inline int make_twiddles(int n, float2** out) {
         case 4096: return CALL(4096);   \
     }
 
+// The tiles one PSD + autocorrelation call hands from pass to pass.  psd_autocorr_impl (b4d_kernels.hip) decides them once per call;
+// the three passes take them as given.
+struct Route {
+    bool parity;           // "ysplit" route of 2048-row frames: parity tiles of ny/2 rows; otherwise tiles of all ny rows
+    int ct_w;              // complex columns per tile
+    const float2* tw_col;  // twiddles of the transform the column pass runs: ny/2 points on parity tiles, ny points otherwise
+};
+
+// Launchers: one per pass, the route (YS: parity tiles) a template argument.  A dispatcher instantiates every kernel it names in the
+// including unit: the plain-route ones (dispatch_r2c, dispatch_c2r) are ordinary functions, the *_route templates let the one unit
+// that runs the parity-tile kernels of a pass build them.
 #if B4D_UNIT_PASSES & B4D_PASS_COL
-#ifndef B4D_COL_SPLIT
-#define B4D_COL_SPLIT 1
-#endif
-template <int NY, int MODE>
-static int launch_col(const ColArgs& a, int ntiles, int batch, hipStream_t st) {
-    constexpr int SPLIT = (NY == 2048 && MODE == COL_PSD_AC) ? B4D_COL_SPLIT : 1;
-    using Cfg = ColCfg<NY, SPLIT>;
+// grid: one workgroup per tile; YS: 1024-point parity tiles of 2048-row frames, a.tw / a.tw_inv = 1024-point twiddles
+template <int NY, int MODE, int YS = 0>
+static int launch_col(const ColArgs& a, int batch, hipStream_t st) {
+    using Cfg = ColCfg<NY, YS>;
+    if ((a.nx / 2) % Cfg::CT) return fail(B4D_ESIZE, "column pass: nx / 2 is no multiple of the tile width");
     {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<NY, MODE, SPLIT, B4D_UNIT_TAG>), Cfg::LDS_BYTES);
+        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<NY, MODE, B4D_UNIT_TAG, YS>), Cfg::LDS_BYTES);
         if (rc_lds) return rc_lds;
     }
-    hipLaunchKernelGGL((k_col<NY, MODE, SPLIT, B4D_UNIT_TAG>), dim3(ntiles * SPLIT, batch), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, a);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-// "ysplit" route (ny = 2048): 1024-point parity tiles, a.tw / a.tw_inv = 1024-point twiddles; grid (2 nt', batch)
-template <int YS = 1>
-static int launch_col_ys(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {
-    using Cfg = ColCfg<1024, 1, YS>;
-    if (pl->ny != 2048 || (pl->nx / 2) % Cfg::CT) return fail(B4D_ESIZE, "ysplit column pass: unsupported size");
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<1024, COL_PSD_AC, 1, B4D_UNIT_TAG, YS>), Cfg::LDS_BYTES);
-        if (rc_lds) return rc_lds;
-    }
-    hipLaunchKernelGGL((k_col<1024, COL_PSD_AC, 1, B4D_UNIT_TAG, YS>), dim3(2 * ((pl->nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
+    hipLaunchKernelGGL((k_col<NY, MODE, B4D_UNIT_TAG, YS>), dim3((YS ? 2 : 1) * ((a.nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
                        Cfg::LDS_BYTES, st, a);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
 template <int MODE>
 static int dispatch_col(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {
-    const int ntiles = (pl->nx / 2) / pl->ct_w;
-#define B4D_CALL(N) launch_col<N, MODE>(a, ntiles, batch, st)
+#define B4D_CALL(N) launch_col<N, MODE>(a, batch, st)
     B4D_SIZE_SWITCH(pl->ny, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported ny");
@@ -1088,77 +1022,73 @@ static int dispatch_nyq(const b4d_plan* pl, NyqArgs a, int items, hipStream_t st
 #endif  // B4D_PASS_NYQ
 
 #if B4D_UNIT_PASSES & B4D_PASS_R2C
-template <int NX>
-static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, const RowSrc* srcs, int batch,
+// YS: rows p and p + ny/2 per transform, parity tile sets (full frames only); otherwise srcs != null selects ROI / z-score sources
+template <int NX, bool YS>
+static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, const RowSrc* srcs, int ct_w, int batch,
                       hipStream_t st) {
     constexpr int SEQ = row_seq(NX);
     constexpr int ITER = NX >= 1024 ? B4D_K1_ITER : 1;   // groups of row pairs per workgroup, full frames only
-    const dim3 block((NX / E16) * SEQ);
-    if (srcs)
-        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, true>), dim3((pl->ny / 2 + SEQ - 1) / SEQ, batch), block, 0, st, in, spec, nyq_rows,
-                           pl->tw_x, pl->ny, pl->ct_w, srcs, (const float2*)nullptr);
+    const dim3 block((NX / E16) * SEQ), grid((pl->ny / 2 + SEQ - 1) / SEQ, batch),
+        grid_full((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch);
+    if (YS && srcs) return fail(B4D_EINVAL, "parity tiles take full frames");
+    if constexpr (YS)
+        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, srcs,
+                           pl->tw_y);
+    else if (srcs)
+        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, true>), grid, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, srcs,
+                           (const float2*)nullptr);
     else
-        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER>), dim3((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch), block, 0, st,
-                           in, spec, nyq_rows, pl->tw_x, pl->ny, pl->ct_w, srcs, (const float2*)nullptr);
+        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, srcs,
+                           (const float2*)nullptr);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
-// "ysplit" route: rows p and p + ny/2 per transform, parity tile sets of ct_w columns (a template so that only the unit that
-// calls it instantiates the kernels)
-template <int NX>
-static int launch_r2c_ys(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, int ct_w, int batch, hipStream_t st) {
-    constexpr int SEQ = row_seq(NX);
-    constexpr int ITER = NX >= 1024 ? B4D_K1_ITER : 1;
-    hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true>), dim3((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch),
-                       dim3((NX / E16) * SEQ), 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, (const RowSrc*)nullptr, pl->tw_y);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-template <int DUMMY = 0>
-static int dispatch_r2c_ys(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows, int ct_w) {
-#define B4D_CALL(N) launch_r2c_ys<N>(pl, in, spec, nyq_rows, ct_w, batch, st)
+template <bool YS>
+static int dispatch_r2c_route(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows,
+                              const RowSrc* srcs, int ct_w) {
+#define B4D_CALL(N) launch_r2c<N, YS>(pl, in, spec, nyq_rows, srcs, ct_w, batch, st)
     B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported nx");
 }
-// rows -> half spectra into `spec` / `nyq_rows` (default: the plan's chunk workspace); srcs != null selects
+// rows -> half spectra into `spec` / `nyq_rows` (default: the plan's chunk workspace), tiles of all ny rows; srcs != null selects
 // ROI / z-score sources
 static int dispatch_r2c(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec = nullptr,
                         float* nyq_rows = nullptr, const RowSrc* srcs = nullptr) {
-    if (!spec) spec = pl->spec;
-    if (!nyq_rows) nyq_rows = pl->nyq_rows;
-#define B4D_CALL(N) launch_r2c<N>(pl, in, spec, nyq_rows, srcs, batch, st)
-    B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
-#undef B4D_CALL
-    return fail(B4D_ESIZE, "unsupported nx");
+    return dispatch_r2c_route<false>(pl, in, batch, st, spec ? spec : pl->spec, nyq_rows ? nyq_rows : pl->nyq_rows, srcs, pl->ct_w);
 }
 #endif  // B4D_PASS_R2C
 
 #if B4D_UNIT_PASSES & B4D_PASS_C2R
-// mode: C2R_OUT (with a C2R_PEAK pre-pass when NORM_PEAK) or C2R_MAG.  ev: optional event sink (timed runs).
-template <int NX>
+// mode: C2R_OUT (with a C2R_PEAK pre-pass when NORM_PEAK), C2R_MAG or C2R_ROWS.  ev: optional event sink (timed runs).
+// YS: C2R_OUT on the parity tiles (a.ct_w, a.tw_y), always the half form.
+template <int NX, bool YS>
 static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mode, hipStream_t st,
                       std::vector<hipEvent_t>* ev, int* nblk) {
     constexpr int SEQ = row_seq(NX);
-    const int npairs = (a.half && mode == C2R_OUT) ? pl->ny / 4 + 1 : pl->ny / 2;
+    const int npairs = (YS || (a.half && mode == C2R_OUT)) ? pl->ny / 4 + 1 : pl->ny / 2;
     const dim3 grid((npairs + SEQ - 1) / SEQ, batch), block((NX / E16) * SEQ);
     if (nblk) *nblk = grid.x;
     if (batch < 1) return B4D_OK;
-    if (mode == C2R_MAG) {
-        // with a.gate (full maps for the few frames that need them) the workgroups of every other frame leave at once; a loop
-        // over row blocks inside the kernel instead of the full grid was tried: the compiler hoists the transform's twiddle
-        // and address set out of it (92 -> 236 VGPRs, half the occupancy of the main pass that shares the instantiation)
-        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_MAG, B4D_UNIT_TAG>), grid, block, 0, st, a);
-        B4D_HIP(hipGetLastError());
-        return B4D_OK;
-    }
-    if (mode == C2R_ROWS) {   // three row pairs around each frame's peak (a.nblk partials per frame)
-        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_ROWS, B4D_UNIT_TAG>), dim3((3 + SEQ - 1) / SEQ, batch), block, 0, st, a);
-        B4D_HIP(hipGetLastError());
-        return B4D_OK;
+    if constexpr (YS) {
+        if (mode != C2R_OUT) return fail(B4D_EINVAL, "parity tiles: autocorrelation output only");
+    } else {
+        if (mode == C2R_MAG) {
+            // with a.gate (full maps for the few frames that need them) the workgroups of every other frame leave at once; a loop
+            // over row blocks inside the kernel instead of the full grid was tried: the compiler hoists the transform's twiddle
+            // and address set out of it (92 -> 236 VGPRs, half the occupancy of the main pass that shares the instantiation)
+            hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_MAG, B4D_UNIT_TAG>), grid, block, 0, st, a);
+            B4D_HIP(hipGetLastError());
+            return B4D_OK;
+        }
+        if (mode == C2R_ROWS) {   // three row pairs around each frame's peak (a.nblk partials per frame)
+            hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_ROWS, B4D_UNIT_TAG>), dim3((3 + SEQ - 1) / SEQ, batch), block, 0, st, a);
+            B4D_HIP(hipGetLastError());
+            return B4D_OK;
+        }
     }
     if (a.flags & B4D_NORM_PEAK) {
-        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_PEAK, B4D_UNIT_TAG>), dim3(1, batch), block, 0, st, a);
+        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_PEAK, B4D_UNIT_TAG, YS>), dim3(1, batch), block, 0, st, a);
         B4D_HIP(hipGetLastError());
         if (ev) {
             hipEvent_t e;
@@ -1167,42 +1097,20 @@ static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mo
             B4D_HIP(hipEventRecord(e, st));
         }
     }
-    hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS>), grid, block, 0, st, a);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
-// "ysplit" route: C2R_OUT on the parity tiles (a.ct_w, a.tw_y), with the same zero-lag pre-pass when NORM_PEAK
-template <int NX>
-static int launch_c2r_ys(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev) {
-    constexpr int SEQ = row_seq(NX);
-    const dim3 grid((pl->ny / 4 + 1 + SEQ - 1) / SEQ, batch), block((NX / E16) * SEQ);
-    if (batch < 1) return B4D_OK;
-    if (a.flags & B4D_NORM_PEAK) {
-        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_PEAK, B4D_UNIT_TAG, true>), dim3(1, batch), block, 0, st, a);
-        B4D_HIP(hipGetLastError());
-        if (ev) {
-            hipEvent_t e;
-            B4D_HIP(hipEventCreate(&e));
-            ev->push_back(e);
-            B4D_HIP(hipEventRecord(e, st));
-        }
-    }
-    hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, true>), grid, block, 0, st, a);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-template <int DUMMY = 0>
-static int dispatch_c2r_ys(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev) {
-#define B4D_CALL(N) launch_c2r_ys<N>(pl, a, batch, st, ev)
+template <bool YS>
+static int dispatch_c2r_route(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, int mode, std::vector<hipEvent_t>* ev,
+                              int* nblk) {
+#define B4D_CALL(N) launch_c2r<N, YS>(pl, a, batch, mode, st, ev, nblk)
     B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported nx");
 }
 static int dispatch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, int mode = C2R_OUT,
                         std::vector<hipEvent_t>* ev = nullptr, int* nblk = nullptr) {
-#define B4D_CALL(N) launch_c2r<N>(pl, a, batch, mode, st, ev, nblk)
-    B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
-#undef B4D_CALL
-    return fail(B4D_ESIZE, "unsupported nx");
+    return dispatch_c2r_route<false>(pl, a, batch, st, mode, ev, nblk);
 }
 #endif  // B4D_PASS_C2R

@@ -238,6 +238,13 @@ static unsigned long long* g_diag = nullptr;
 extern "C" void b4d_debug_set_diag(void* buf) { g_diag = static_cast<unsigned long long*>(buf); }
 #endif
 
+// Forward row pass of the PSD + autocorrelation pipeline on the call's route: this unit's counterpart of col_psd_ac_pass and
+// row_out_pass (b4d_passes.hpp), and the only place that builds the parity-tile k_row_r2c.
+static int row_in_pass(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows, const Route& rt) {
+    return rt.parity ? dispatch_r2c_route<true>(pl, in, batch, st, spec, nyq_rows, nullptr, rt.ct_w)
+                     : dispatch_r2c(pl, in, batch, st, spec, nyq_rows);
+}
+
 // Shared body.  With `kernel_ms` != null every kernel launch is bracketed by HIP events on `st`
 // and the per-kernel elapsed times (ms; row R2C, column, peak, row C2R) are ADDED to kernel_ms[0..3]
 // after a final hipEventSynchronize -- used by bench.py to price each kernel inside its timed region.
@@ -252,8 +259,8 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
     const size_t fpix = (size_t)pl->ny * pl->nx;
     // one route per call, chosen by the frame shape alone (never by batch, chunk or lanes): 2048-row frames take the parity-tile
     // route, where the row passes do one radix-2 stage of the column transform
-    const int ysplit = (pl->ny == 2048 && pl->tw_yh) ? g_opt_ysplit.load() : 0;
-    constexpr int ys_ct = ColCfg<1024, 1, 1>::CT;   // columns per parity tile
+    const bool parity = pl->ny == 2048 && pl->tw_yh && g_opt_ysplit.load();
+    const Route rt = parity ? Route{true, ColCfg<1024, 1>::CT, pl->tw_yh} : Route{false, pl->ct_w, pl->tw_y};
     std::vector<hipEvent_t> ev;
     auto mark = [&]() -> int {
         if (!kernel_ms) return B4D_OK;
@@ -280,14 +287,12 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
         float* nyq_rows = pl->nyq_rows + (size_t)pl->ny * so;
         float* gnyq = pl->gnyq + (size_t)pl->ny * so;
         if ((rc = mark())) break;
-        if ((rc = ysplit ? dispatch_r2c_ys(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows, ys_ct)
-                         : dispatch_r2c(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows)))
-            break;
+        if ((rc = row_in_pass(pl, frames + b0 * fpix, nb, ls, spec, nyq_rows, rt))) break;
         if ((rc = mark())) break;
         ColArgs ca{};
         ca.spec = spec;
         ca.psd = psd ? psd + b0 * fpix : nullptr;
-        ca.tw = ysplit ? pl->tw_yh : pl->tw_y;
+        ca.tw = rt.tw_col;
         ca.tw_inv = ca.tw;
         ca.psd_scale = psd_scale;
         ca.nx = pl->nx;
@@ -296,7 +301,7 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
 #ifdef B4D_DIAG
         ca.diag = g_diag;
 #endif
-        if ((rc = col_psd_ac_pass(pl, ca, nb, ls, ysplit))) break;
+        if ((rc = col_psd_ac_pass(pl, ca, nb, ls, rt))) break;
         NyqArgs na{};
         na.rows = nyq_rows;
         na.g_out = gnyq;
@@ -313,11 +318,11 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
             ra.tw = pl->tw_x;
             ra.scale = 1.0f / ((float)pl->nx * (float)pl->ny);
             ra.ny = pl->ny;
-            ra.ct_w = ysplit ? ys_ct : pl->ct_w;
+            ra.ct_w = rt.ct_w;
             ra.tw_y = pl->tw_y;
             ra.flags = flags;
             ra.half = 1;
-            if ((rc = row_out_pass(pl, ra, nb, ls, kernel_ms ? &ev : nullptr, ysplit))) break;
+            if ((rc = row_out_pass(pl, ra, nb, ls, kernel_ms ? &ev : nullptr, rt))) break;
         }
         if ((rc = mark())) break;
     }

@@ -13,7 +13,7 @@
 #include "b4d_fft2d.hpp"
 
 namespace b4d {
-// ysplit: 0 = tiles of all ny rows; 1 = the "ysplit" route of 2048-row frames (parity tiles, b4d_fft2d.hpp)
-int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, int ysplit);
-int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, int ysplit);
+// rt: the call's route (Route, b4d_fft2d.hpp): tiles of all ny rows, or the parity tiles of the "ysplit" route of 2048-row frames
+int col_psd_ac_pass(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st, const Route& rt);
+int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, const Route& rt);
 }  // namespace b4d

@@ -5,8 +5,7 @@
 #include "b4d_passes.hpp"
 
 namespace b4d {
-int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, int ysplit) {
-    if (ysplit) return dispatch_c2r_ys(pl, a, batch, st, ev);
-    return dispatch_c2r(pl, a, batch, st, C2R_OUT, ev);
+int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, const Route& rt) {
+    return rt.parity ? dispatch_c2r_route<true>(pl, a, batch, st, C2R_OUT, ev, nullptr) : dispatch_c2r(pl, a, batch, st, C2R_OUT, ev);
 }
 }  // namespace b4d

@@ -69,7 +69,7 @@ k_col_r2c(const float* __restrict__ frames, float2* __restrict__ half, const flo
         v[0][j] = make_float2(q.x, q.y);
         v[1][j] = make_float2(q.z, q.w);
     }
-    Fft3<G, 1>::template run_sets<2, true, true, 1>(v, u, cp, lds, tw);
+    Fft3<G, 1>::template run_sets<2>(v, u, cp, lds, tw);
     // v[s][j] = Z_s[ky = u + T j].  Columns a, b of z = a + i b:  A[ky] = (Z[ky] + conj Z[-ky]) / 2,  B[ky] = (Z[ky] - conj Z[-ky]) / 2i.
     // Only ky < ny/2 is kept (j < 8): the partners -ky live in the upper half (j >= 8), which goes through the exchange buffer
     // -- both sets at once (2 x ny/2 x CPT values fit the region of one transform set).

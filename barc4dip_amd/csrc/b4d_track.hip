@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(ColCfg<NY>::THREADS, ColCfg<NY>::WAVES_PER_EU)
                 v[2 * h + 1][j] = make_float2(q.z, q.w);
             }
         }
-        Fft3<G, 1>::template run_sets<NC, Cfg::SERIAL, true, Cfg::SB>(v, u, cp, lds, p.tw);
+        Fft3<G, 1>::template run_sets<NC>(v, u, cp, lds, p.tw);
         // v[c][j] = Ft[ky = u + T j][column c]: the product with the image tile replaces it in place
         int tid1 = threadIdx.x;   // lane position derived again: the first transform's index set need not stay live (cf. k_col)
         asm volatile("" : "+v"(tid1));
@@ -185,7 +185,7 @@ __global__ void __launch_bounds__(ColCfg<NY>::THREADS, ColCfg<NY>::WAVES_PER_EU)
     {
         int tid2 = threadIdx.x;
         asm volatile("" : "+v"(tid2));
-        Fft3<G, 1>::template run_sets<NC, Cfg::SERIAL, true, Cfg::SB>(v, tid2 / CPT, tid2 % CPT, lds, TPL ? p.tw2 : p.tw);
+        Fft3<G, 1>::template run_sets<NC>(v, tid2 / CPT, tid2 % CPT, lds, TPL ? p.tw2 : p.tw);
     }
     unsigned toff2 = toff;   // laundered: the store addresses are not kept live across the transform (spills otherwise)
     asm volatile("" : "+v"(toff2));
