@@ -105,6 +105,14 @@ struct Mix3 {
             for (int k3 = 0; k3 < R3; ++k3) p[k3] = v[k3];
         }
     }
+    // stages 2 and 3 behind a stage 1 whose writes are not fenced yet; the result is fenced on return
+    static __device__ __forceinline__ void stages23(float2* __restrict__ buf, const float2* __restrict__ tw2, int tid) {
+        __syncthreads();
+        stage2(buf, tw2, tid);
+        __syncthreads();
+        stage3(buf, tid);
+        __syncthreads();
+    }
 };
 
 }  // namespace b4d

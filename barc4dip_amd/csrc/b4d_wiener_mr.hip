@@ -20,6 +20,8 @@
 //                   crop folded into the store.
 // The row kernels keep 140 KB of LDS (4 x 34 KB row buffers), i.e. one 1024-lane workgroup per CU: they are persistent
 // (grid = CUs, a loop over quads) and issue the next quad's frame loads before the current quad's store loop.
+// Shared by the kernels: QuadLoop (the loop over quads), quad_lane (per-iteration lane context and why it is opaque),
+// Mix3::stages23 (b4d_mixed.hpp); on the host wmr_for_length (length -> Mix3 type) and launch_rows.
 // The reference divides the padded frame by max|.| BEFORE the (linear) filter and multiplies back after the clip; here
 // the division is applied to the filtered value just before the clip -- the same real-number result, different by one
 // float32 rounding of the scale (the maximum is only known after the first pass over the frame).
@@ -62,6 +64,52 @@ __device__ __forceinline__ QuadRef quad_of(int j, int qpf, int qpf2, int nframes
     return q;
 }
 
+// The persistent loop of a row kernel over the quads of a launch:
+//   const QuadLoop ql(qpf, nframes);  for (int q = ql.first(); !ql.done(q); q = ql.next(q)) { const QuadRef qr = ql.at(q); ... }
+struct QuadLoop {
+    int qpf, qpf2, nframes, nitems;
+    __device__ __forceinline__ QuadLoop(int qpf_, int nframes_)
+        : qpf(qpf_), qpf2((qpf_ + 1) & ~1), nframes(nframes_), nitems((nframes_ * qpf2 + 15) & ~15) {}
+    __device__ __forceinline__ QuadRef at(int j) const { return quad_of(j, qpf, qpf2, nframes); }
+    // next work item of this workgroup after j that maps to a real quad (done() if none)
+    __device__ __forceinline__ int next(int j) const {
+        for (j += gridDim.x; j < nitems && !at(j).valid; j += gridDim.x) {}
+        return j;
+    }
+    __device__ __forceinline__ int first() const { return next((int)blockIdx.x - (int)gridDim.x); }
+    __device__ __forceinline__ bool done(int j) const { return j >= nitems; }
+};
+
+// What a lane needs inside one iteration of the quad loop, rebuilt every iteration from OPAQUE copies of the lane indices and
+// the twiddle pointer.  Everything derived from the lane index or the tables is invariant in q: left alone, the compiler
+// precomputes all of it (twiddle loads included) ahead of the quad loop and spills > 100 dwords around the radix stages; the
+// opaque copies keep those values short-lived.
+template <class MX>
+struct QuadLane {
+    int lt, tid;          // lane of the group, lane of the workgroup
+    const float2* twN;
+    int sub;              // group = pair of the quad this lane transforms
+    float2* buf;          // that pair's row buffer
+    const float2* tw2;
+    // The stages have M1 / M2 / M3 items for L lanes, so each leaves the group's last waves idle (radix 27: 152 items,
+    // waves 2.4 .. 3).  Wave w of every group sits on SIMD w % 4: rotating the item <-> lane map by one wave per
+    // group spreads the idle waves over the four SIMDs instead of parking all of them on SIMD 3.
+    int ltr;
+};
+template <class MX>
+__device__ __forceinline__ QuadLane<MX> quad_lane(int lt, int tid, const float2* twN, float2* sm) {
+    asm volatile("" : "+v"(lt), "+v"(tid), "+s"(twN));
+    QuadLane<MX> c;
+    c.lt = lt;
+    c.tid = tid;
+    c.twN = twN;
+    c.sub = tid / MX::LANES;
+    c.buf = sm + (size_t)c.sub * MX::BUF;
+    c.tw2 = sm + (size_t)WMR_Q * MX::BUF;
+    c.ltr = (lt + 64 * c.sub) % MX::LANES;
+    return c;
+}
+
 template <class MX>
 __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_fwd(const float* __restrict__ frames, float2* __restrict__ T,
                                                                     const float2* __restrict__ twN, float* __restrict__ pmax, WmrGeom g,
@@ -75,12 +123,13 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_fwd(const float* 
 
     float2 v[RD][R1];
     float mx = 0.f;
-    // frame loads of quad q for this lane's pair (compute mapping: lane lt of group sub owns items lt, lt + L, ...)
+    // QuadLoop as inline text: through the struct this kernel compiles to different code
     const int qpf2 = (qpf + 1) & ~1, nitems = (nframes * qpf2 + 15) & ~15;
     auto next_item = [&](int j) {   // next work item of this workgroup that maps to a real quad (nitems if none)
         for (j += gridDim.x; j < nitems && !quad_of(j, qpf, qpf2, nframes).valid; j += gridDim.x) {}
         return j;
     };
+    // frame loads of quad q for this lane's pair (compute mapping: lane lt of group sub owns items lt, lt + L, ...)
     auto load = [&](int j, int lt, int sub) {
         const QuadRef qr = quad_of(j, qpf, qpf2, nframes);
         const int f = qr.f, pr = WMR_Q * qr.qi + sub;
@@ -115,48 +164,36 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_fwd(const float* 
     int q = next_item((int)blockIdx.x - (int)gridDim.x);
     if (B4D_WMR_PREFETCH && q < nitems) load(q, (lt + 64 * (tid / L)) % L, tid / L);
     for (; q < nitems; q = next_item(q)) {
-        // Everything derived from the lane index or the tables is invariant in q: left alone, the compiler precomputes all of
-        // it (twiddle loads included) ahead of the quad loop and spills > 100 dwords around the radix stages.  Opaque
-        // per-iteration copies keep those values short-lived.
-        int ltq = lt, tidq = tid;
-        const float2* twq = twN;
-        asm volatile("" : "+v"(ltq), "+v"(tidq), "+s"(twq));
-        const int subq = tidq / L;
-        float2* bufq = sm + (size_t)subq * MX::BUF;
-        const float2* tw2q = sm + (size_t)WMR_Q * MX::BUF;
+        const QuadLane<MX> ln = quad_lane<MX>(lt, tid, twN, sm);
         const QuadRef qr = quad_of(q, qpf, qpf2, nframes);
-        const int f = qr.f, qi = qr.qi, pr = WMR_Q * qi + subq;
+        const int f = qr.f, qi = qr.qi, pr = WMR_Q * qi + ln.sub;
         const bool act = pr < g.hp;
-        // The stages have M1 / M2 / M3 items for L lanes, so each leaves the group's last waves idle (radix 27: 152 items,
-        // waves 2.4 .. 3).  Wave w of every group sits on SIMD w % 4: rotating the item <-> lane map by one wave per
-        // group spreads the idle waves over the four SIMDs instead of parking all of them on SIMD 3.
-        const int ltr = (ltq + 64 * subq) % L;
-        if (!B4D_WMR_PREFETCH) load(q, ltr, subq);
+        if (!B4D_WMR_PREFETCH) load(q, ln.ltr, ln.sub);
 #pragma unroll
         for (int r = 0; r < RD; ++r) {
-            const int m = ltr + r * L;
-            if (m < M1) MX::stage1_item(v[r], m, bufq, twq);
+            const int m = ln.ltr + r * L;
+            if (m < M1) MX::stage1_item(v[r], m, ln.buf, ln.twN);
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_down(mx, o, 64));
-        if ((tidq & 63) == 0) wmax[tidq >> 6] = mx;
+        if ((ln.tid & 63) == 0) wmax[ln.tid >> 6] = mx;
         __syncthreads();
-        if (ltq == 0 && act) {
-            float m2 = wmax[subq * (L / 64)];
+        if (ln.lt == 0 && act) {
+            float m2 = wmax[ln.sub * (L / 64)];
 #pragma unroll
-            for (int i = 1; i < L / 64; ++i) m2 = fmaxf(m2, wmax[subq * (L / 64) + i]);
+            for (int i = 1; i < L / 64; ++i) m2 = fmaxf(m2, wmax[ln.sub * (L / 64) + i]);
             pmax[(size_t)f * g.hp + pr] = m2;
         }
-        MX::stage2(bufq, tw2q, ltr);
+        MX::stage2(ln.buf, ln.tw2, ln.ltr);
         __syncthreads();
-        MX::stage3(bufq, ltr);
+        MX::stage3(ln.buf, ln.ltr);
         __syncthreads();
         {
             const int qn = next_item(q);
-            if (B4D_WMR_PREFETCH && qn < nitems) load(qn, ltr, subq);   // in flight under the store loop
+            if (B4D_WMR_PREFETCH && qn < nitems) load(qn, ln.ltr, ln.sub);   // in flight under the store loop
         }
         // piece mapping: lanes 4 i .. 4 i + 3 hold the four pairs' pieces of ONE k: 64 contiguous bytes of T[k][.]
-        const int j = tidq & (WMR_Q - 1), kk = tidq / WMR_Q;
+        const int j = ln.tid & (WMR_Q - 1), kk = ln.tid / WMR_Q;
         const float2* bj = sm + (size_t)j * MX::BUF;
         const bool wr = WMR_Q * qi + j < g.hp;
         float2* dst = T + (size_t)f * g.Wh * g.Hp + 2 * (WMR_Q * qi + j);
@@ -231,11 +268,7 @@ __global__ void __launch_bounds__(MY::LANES, 4) k_wmr_cols(float2* __restrict__ 
             for (int n1 = 0; n1 < R1; ++n1) fv[r][n1] = fl[M1 * n1 + mc];
         }
     }
-    __syncthreads();
-    MY::stage2(buf, tw2, tid);
-    __syncthreads();
-    MY::stage3(buf, tid);
-    __syncthreads();
+    MY::stages23(buf, tw2, tid);
     if (MODE == 2) {
         typename MY::template PosIter<LANES> pf(tid);
         for (int n = tid; n < N; n += LANES) {
@@ -279,11 +312,7 @@ __global__ void __launch_bounds__(MY::LANES, 4) k_wmr_cols(float2* __restrict__ 
         const int m = tid + r * LANES;
         if (m < M1) MY::stage1_item(v[r], m, buf, twN);
     }
-    __syncthreads();
-    MY::stage2(buf, tw2, tid);
-    __syncthreads();
-    MY::stage3(buf, tid);
-    __syncthreads();
+    MY::stages23(buf, tw2, tid);
     typename MY::template PosIter<LANES> pk(tid);
     for (int n = tid; n < N; n += LANES) {
         const float2 z = buf[pk.pos()];
@@ -304,31 +333,28 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_inv(const float2*
     // the 16-byte pieces of quad q this lane gathers (piece mapping: k = tid / 4 + i L, pair tid % 4), clamped addresses
     constexpr int NP = (N / 2 + 1 + L - 1) / L;
     float4 pc[NP];
-    const int qpf2 = (qpf + 1) & ~1, nitems = (nframes * qpf2 + 15) & ~15;
-    auto next_item = [&](int j) {
-        for (j += gridDim.x; j < nitems && !quad_of(j, qpf, qpf2, nframes).valid; j += gridDim.x) {}
-        return j;
-    };
+    const QuadLoop ql(qpf, nframes);
     auto fetch = [&](int j, int tidq) {
-        const QuadRef qr = quad_of(j, qpf, qpf2, nframes);
+        const QuadRef qr = ql.at(j);
         const int f = qr.f, pj = WMR_Q * qr.qi + (tidq & (WMR_Q - 1)), kk = tidq / WMR_Q;
         const float2* src = T + (size_t)f * g.Wh * g.Hp + 2 * min(pj, g.hp - 1);
 #pragma unroll
         for (int i = 0; i < NP; ++i) pc[i] = *reinterpret_cast<const float4*>(src + (size_t)min(kk + i * L, g.Wh - 1) * g.Hp);
     };
-    int q = next_item((int)blockIdx.x - (int)gridDim.x);
-    if (B4D_WMR_PREFETCH && q < nitems) fetch(q, tid);
-    for (; q < nitems; q = next_item(q)) {
-        int ltq = lt, tidq = tid;   // opaque per-iteration copies (see k_wmr_rows_fwd)
+    int q = ql.first();
+    if (B4D_WMR_PREFETCH && !ql.done(q)) fetch(q, tid);
+    for (; !ql.done(q); q = ql.next(q)) {
+        int ltq = lt, tidq = tid;   // quad_lane() as inline text: through the helper this kernel compiles to different code
         const float2* twq = twN;
         asm volatile("" : "+v"(ltq), "+v"(tidq), "+s"(twq));
         const int subq = tidq / L;
         float2* bufq = sm + (size_t)subq * MX::BUF;
         const float2* tw2q = sm + (size_t)WMR_Q * MX::BUF;
-        const QuadRef qr = quad_of(q, qpf, qpf2, nframes);
+        const QuadRef qr = ql.at(q);
         const int f = qr.f, qi = qr.qi, pr = WMR_Q * qi + subq;
         {   // piece mapping: four neighbouring lanes gather the four pairs' 16-byte pieces of ONE k (a 64-byte sector);
-            // Ga + i Gb, Hermitian-extended beyond N/2, conjugated for the inverse, lands in natural order in the pair's buffer
+            // Ga + i Gb, Hermitian-extended beyond N/2, conjugated for the inverse, lands in natural order in the pair's buffer.
+            // (Kept as inline text in the three kernels that have it: as a shared function it reschedules the 171-point kernels.)
             const int j = tidq & (WMR_Q - 1), kk = tidq / WMR_Q, pj = WMR_Q * qi + j;
             float2* bj = sm + (size_t)j * MX::BUF;
             const bool hb = 2 * pj + 1 < g.H;
@@ -345,7 +371,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_inv(const float2*
             }
         }
         __syncthreads();
-        const int ltr = (ltq + 64 * subq) % L;   // item <-> lane map rotated by one wave per group (see k_wmr_rows_fwd)
+        const int ltr = (ltq + 64 * subq) % L;
         float2 v[RD][R1];
 #pragma unroll
         for (int r = 0; r < RD; ++r) {
@@ -359,11 +385,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_inv(const float2*
             const int m = ltr + r * L;
             if (m < M1) MX::stage1_item(v[r], m, bufq, twq);
         }
-        __syncthreads();
-        MX::stage2(bufq, tw2q, ltr);
-        __syncthreads();
-        MX::stage3(bufq, ltr);
-        __syncthreads();
+        MX::stages23(bufq, tw2q, ltr);
         // np: work = padded / scale; restored = clip(wiener(work)) * scale (filters.py:259-266, 287): the 1/(H W) of the
         // inverse transform and the division by the scale are one factor here
         const float fsc = amax[f];
@@ -374,8 +396,8 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_inv(const float2*
         const bool wa = act && ya >= 0 && ya < g.h, wb = act && r0 + 1 < g.H && yb >= 0 && yb < g.h;
         float* orow = out + ((size_t)f * g.h + ya) * g.w;
         {
-            const int qn = next_item(q);
-            if (B4D_WMR_PREFETCH && qn < nitems) fetch(qn, tidq);   // in flight under the store loop
+            const int qn = ql.next(q);
+            if (B4D_WMR_PREFETCH && !ql.done(qn)) fetch(qn, tidq);   // in flight under the store loop
         }
         typename MX::template PosIter<L> pk(ltq + g.px);
         for (int x = ltq; x < g.w; x += L) {
@@ -428,11 +450,7 @@ __global__ void __launch_bounds__(MY::LANES, 4) k_wmr_cols_prod(const float2* __
         const int m = tid + r * LANES;
         if (m < M1) MY::stage1_item(v[r], m, buf, twN);
     }
-    __syncthreads();
-    MY::stage2(buf, tw2, tid);
-    __syncthreads();
-    MY::stage3(buf, tid);
-    __syncthreads();
+    MY::stages23(buf, tw2, tid);
     typename MY::template PosIter<LANES> pk(tid);
     for (int n = tid; n < N; n += LANES) {
         const float2 z = buf[pk.pos()];
@@ -457,6 +475,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
     int* si = reinterpret_cast<int*>(sv + WG / 64);
     unsigned* hl = reinterpret_cast<unsigned*>(si + WG / 64);   // 2 (WG / 64) + 1 words: the median's expected-bin bookkeeping
     for (int t = tid; t < M1; t += WG) tw2[t] = twN[R1 * t];
+    // QuadLoop as inline text: through the struct this kernel compiles to different code
     const int qpf2 = (qpf + 1) & ~1, nitems = (nframes * qpf2 + 15) & ~15;
     auto next_item = [&](int j) {
         for (j += gridDim.x; j < nitems && !quad_of(j, qpf, qpf2, nframes).valid; j += gridDim.x) {}
@@ -464,7 +483,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
     };
     const size_t fpix = (size_t)g.H * g.W;
     for (int q = next_item((int)blockIdx.x - (int)gridDim.x); q < nitems; q = next_item(q)) {
-        int ltq = lt, tidq = tid;   // opaque per-iteration copies (see k_wmr_rows_fwd)
+        int ltq = lt, tidq = tid;   // quad_lane() as inline text: through the helper this kernel compiles to different code
         const float2* twq = twN;
         asm volatile("" : "+v"(ltq), "+v"(tidq), "+s"(twq));
         const int subq = tidq / L;
@@ -502,11 +521,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
             const int m = ltr + r * L;
             if (m < M1) MX::stage1_item(v[r], m, bufq, twq);
         }
-        __syncthreads();
-        MX::stage2(bufq, tw2q, ltr);
-        __syncthreads();
-        MX::stage3(bufq, ltr);
-        __syncthreads();
+        MX::stages23(bufq, tw2q, ltr);
         const int ra = (r0 + g.H / 2) % g.H, rb = (r0 + 1 + g.H / 2) % g.H;
         float* mf = mag + (size_t)f * fpix;
         float bv = -1.0f;
@@ -602,14 +617,10 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_spec(const float2
     constexpr int L = MX::LANES;
     static_assert(MX::BUF >= MX::N + 2, "row buffer too small to stage two half rows");
     const int tid = threadIdx.x, lt = tid % L, sub = tid / L;
-    const int qpf2 = (qpf + 1) & ~1, nitems = (nframes * qpf2 + 15) & ~15;
-    auto next_item = [&](int j) {
-        for (j += gridDim.x; j < nitems && !quad_of(j, qpf, qpf2, nframes).valid; j += gridDim.x) {}
-        return j;
-    };
+    const QuadLoop ql(qpf, nframes);
     const size_t fpix = (size_t)g.H * g.W;
-    for (int q = next_item((int)blockIdx.x - (int)gridDim.x); q < nitems; q = next_item(q)) {
-        const QuadRef qr = quad_of(q, qpf, qpf2, nframes);
+    for (int q = ql.first(); !ql.done(q); q = ql.next(q)) {
+        const QuadRef qr = ql.at(q);
         const int f = qr.f, qi = qr.qi;
         {
             const int j = tid & (WMR_Q - 1), kk = tid / WMR_Q, pj = WMR_Q * qi + j;
@@ -675,20 +686,16 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_out(const float2*
     const int tid = threadIdx.x, lt = tid % L;
     float2* tw2 = sm + (size_t)WMR_Q * MX::BUF;
     for (int t = tid; t < M1; t += WG) tw2[t] = twN[R1 * t];
-    const int qpf2 = (qpf + 1) & ~1, nitems = (nframes * qpf2 + 15) & ~15;
-    auto next_item = [&](int j) {
-        for (j += gridDim.x; j < nitems && !quad_of(j, qpf, qpf2, nframes).valid; j += gridDim.x) {}
-        return j;
-    };
+    const QuadLoop ql(qpf, nframes);
     const size_t fpix = (size_t)g.H * g.W;
-    for (int q = next_item((int)blockIdx.x - (int)gridDim.x); q < nitems; q = next_item(q)) {
-        int ltq = lt, tidq = tid;   // opaque per-iteration copies (see k_wmr_rows_fwd)
+    for (int q = ql.first(); !ql.done(q); q = ql.next(q)) {
+        int ltq = lt, tidq = tid;   // quad_lane() as inline text: through the helper this kernel compiles to different code
         const float2* twq = twN;
         asm volatile("" : "+v"(ltq), "+v"(tidq), "+s"(twq));
         const int subq = tidq / L;
         float2* bufq = sm + (size_t)subq * MX::BUF;
         const float2* tw2q = sm + (size_t)WMR_Q * MX::BUF;
-        const QuadRef qr = quad_of(q, qpf, qpf2, nframes);
+        const QuadRef qr = ql.at(q);
         const int f = qr.f, qi = qr.qi, pr = WMR_Q * qi + subq;
         const bool act = pr < g.hp;
         const int r0 = 2 * pr;
@@ -748,11 +755,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_out(const float2*
             const int m = ltr + r * L;
             if (m < M1) MX::stage1_item(v[r], m, bufq, twq);
         }
-        __syncthreads();
-        MX::stage2(bufq, tw2q, ltr);
-        __syncthreads();
-        MX::stage3(bufq, ltr);
-        __syncthreads();
+        MX::stages23(bufq, tw2q, ltr);
         const float pk = (flags & B4D_NORM_PEAK) ? peak[f] : 0.f;
         const bool unit = (flags & B4D_NORM_PEAK) && pk > 0.f;
         const float se = unit ? 1.0f / pk : g.inv;
@@ -844,117 +847,37 @@ static int wmr_cus() {
 
 // persistent row kernels: one workgroup per CU when a workgroup needs most of the LDS, as many as fit otherwise.  The dynamic-LDS
 // attribute is set once per (kernel address, device): ensure_dynamic_lds (b4d_common.hpp).
-template <class MX, class K>
-static int wmr_rows_launch(K kernel, int nquads, hipStream_t st, size_t* lds_out, int* grid_out) {
+// (The arguments take the kernel's own parameter types, deduced from `kernel` alone: a mismatch is an error at the call.)
+template <class T>
+struct WmrArg {
+    using type = T;
+};
+template <class MX, class... P>
+static int launch_rows(void (*kernel)(P...), int nquads, hipStream_t st, typename WmrArg<P>::type... args) {
     const size_t lds = wmr_rows_lds<MX>();
     int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
     if (rc) return rc;
     const int per_cu = std::max(1, std::min((int)((size_t)160 * 1024 / lds), 2048 / (WMR_Q * MX::LANES)));
-    *lds_out = lds;
-    *grid_out = std::min(nquads, wmr_cus() * per_cu);
-    return B4D_OK;
-}
-
-int wmr_rows_fwd(const float* frames, float2* T, const float2* twx, float* pmax, const WmrGeom& g, int nframes, hipStream_t st) {
-    const int qpf = (g.hp + WMR_Q - 1) / WMR_Q, nquads = nframes * qpf;
-    size_t lds = 0;
-    int grid = 0, rc;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                              \
-    case N_: {                                                                                                                             \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                                   \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_fwd<MX>, nquads, st, &lds, &grid))) return rc;                                          \
-        hipLaunchKernelGGL((k_wmr_rows_fwd<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, frames, T, twx, pmax, g, nframes, qpf);              \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
+    const int grid = std::min(nquads, wmr_cus() * per_cu);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WMR_Q * MX::LANES), lds, st, args...);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
 
-template <int MODE>
-static int wmr_cols_launch(float2* T, const float2* filt, const float2* twy, const float* pmax, float* amax, const WmrGeom& g,
-                           int nframes, float* Pt, unsigned flags, int inverse, hipStream_t st, WmrSep sep = WmrSep{nullptr, nullptr, 0.f}) {
-    const unsigned grid = (unsigned)nframes * (unsigned)g.Wh;
-    switch (g.H) {
-#define X(N_, A_, B_, C_, L_)                                                                                                            \
-    case N_:                                                                                                                             \
-        hipLaunchKernelGGL((k_wmr_cols<Mix3<A_, B_, C_, L_>, MODE>), dim3(grid), dim3(L_), 0, st, T, filt, twy, pmax, amax, g, Pt, flags, \
-                           inverse, sep);                                                                                                \
-        break;
+// fn(Mix3<...>{}) of the compiled length n: the one expansion of the length table into code
+template <class F>
+static int wmr_for_length(int n, const char* pass, F&& fn) {
+    switch (n) {
+#define X(N_, A_, B_, C_, L_) \
+    case N_: return fn(Mix3<A_, B_, C_, L_>{});
         B4D_WMR_LENGTHS(X)
 #undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix column kernel for this length");
     }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return fail(B4D_ESIZE, std::string("no mixed-radix ") + pass + " kernel for this length");
 }
 
-int wmr_cols(float2* T, const float2* filt, const float2* twy, const float* pmax, float* amax, const WmrGeom& g, int nframes,
-             hipStream_t st, const float2* sep_x, const float2* sep_y, float balance) {
-    return wmr_cols_launch<0>(T, filt, twy, pmax, amax, g, nframes, nullptr, 0u, 1, st, WmrSep{sep_x, sep_y, balance});
-}
+int wmr_quads_per_frame(int ny) { return ((ny + 1) / 2 + WMR_Q - 1) / WMR_Q; }
 
-int wmr_psd_autocorr(const float* frames, int nframes, int ny, int nx, const float2* twx, const float2* twy, float2* T, float* Pt,
-                     float* scratch, float* psd, float psd_scale, float* autocorr, unsigned flags, hipStream_t st) {
-    WmrGeom g{};
-    g.h = g.H = ny;
-    g.w = g.W = nx;
-    g.py = g.px = 0;
-    g.Wh = nx / 2 + 1;
-    g.Hp = wmr_pitch(ny);
-    g.hp = (ny + 1) / 2;
-    g.inv = 1.0f / ((float)ny * (float)nx);
-    float* pmax = scratch;                       // (nframes, hp): by-product of the shared forward row kernel, unused here
-    float* peak = scratch + (size_t)nframes * g.hp;
-    int rc;
-    if ((rc = wmr_rows_fwd(frames, T, twx, pmax, g, nframes, st))) return rc;
-    if ((rc = wmr_cols_launch<1>(T, nullptr, twy, nullptr, nullptr, g, nframes, psd ? Pt : nullptr, flags, autocorr ? 1 : 0, st))) return rc;
-    if (autocorr && (flags & B4D_NORM_PEAK)) {
-        hipLaunchKernelGGL(k_wmr_peak, dim3(nframes), dim3(256), 0, st, (const float2*)T, g, peak);
-        B4D_HIP(hipGetLastError());
-    }
-    const int qpf = (g.hp + WMR_Q - 1) / WMR_Q, nquads = nframes * qpf;
-    size_t lds = 0;
-    int grid = 0;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                             \
-    case N_: {                                                                                                                            \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                                  \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_out<MX>, nquads, st, &lds, &grid))) return rc;                                         \
-        hipLaunchKernelGGL((k_wmr_rows_out<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, (const float2*)T, (const float*)Pt, autocorr, psd, \
-                           twx, (const float*)peak, g, nframes, qpf, psd_scale, flags);                                                   \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-
-int wmr_rows_inv(const float2* T, float* out, const float2* twx, const float* amax, const WmrGeom& g, int nframes, hipStream_t st) {
-    const int qpf = (g.hp + WMR_Q - 1) / WMR_Q, nquads = nframes * qpf;
-    size_t lds = 0;
-    int grid = 0, rc;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                              \
-    case N_: {                                                                                                                             \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                                   \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_inv<MX>, nquads, st, &lds, &grid))) return rc;                                          \
-        hipLaunchKernelGGL((k_wmr_rows_inv<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, T, out, twx, amax, g, nframes, qpf);                 \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-
-// ---- general-size correlation on the same passes (b4d_track.hip, b4d_general.hip) -----------------------------------------
 static WmrGeom wmr_plain_geom(int ny, int nx) {
     WmrGeom g{};
     g.h = g.H = ny;
@@ -966,6 +889,65 @@ static WmrGeom wmr_plain_geom(int ny, int nx) {
     return g;
 }
 
+int wmr_rows_fwd(const float* frames, float2* T, const float2* twx, float* pmax, const WmrGeom& g, int nframes, hipStream_t st) {
+    const int qpf = wmr_quads_per_frame(g.H);
+    return wmr_for_length(g.W, "row", [&](auto mx) {
+        using MX = decltype(mx);
+        return launch_rows<MX>(&k_wmr_rows_fwd<MX>, nframes * qpf, st, frames, T, twx, pmax, g, nframes, qpf);
+    });
+}
+
+template <int MODE>
+static int wmr_cols_launch(float2* T, const float2* filt, const float2* twy, const float* pmax, float* amax, const WmrGeom& g,
+                           int nframes, float* Pt, unsigned flags, int inverse, hipStream_t st, WmrSep sep = WmrSep{nullptr, nullptr, 0.f}) {
+    const unsigned grid = (unsigned)nframes * (unsigned)g.Wh;
+    return wmr_for_length(g.H, "column", [&](auto my) {
+        using MY = decltype(my);
+        hipLaunchKernelGGL((k_wmr_cols<MY, MODE>), dim3(grid), dim3(MY::LANES), 0, st, T, filt, twy, pmax, amax, g, Pt, flags, inverse, sep);
+        B4D_HIP(hipGetLastError());
+        return (int)B4D_OK;
+    });
+}
+
+int wmr_cols(float2* T, const float2* filt, const float2* twy, const float* pmax, float* amax, const WmrGeom& g, int nframes,
+             hipStream_t st, const float2* sep_x, const float2* sep_y, float balance) {
+    return wmr_cols_launch<0>(T, filt, twy, pmax, amax, g, nframes, nullptr, 0u, 1, st, WmrSep{sep_x, sep_y, balance});
+}
+
+// the last pass of wmr_psd_autocorr (psd and / or autocorr) and of wmr_rows_real_out (autocorr = the real maps alone)
+static int wmr_rows_out(const float2* T, const float* Pt, float* autocorr, float* psd, const float2* twx, const float* peak, const WmrGeom& g,
+                        int nframes, float psd_scale, unsigned flags, hipStream_t st) {
+    const int qpf = wmr_quads_per_frame(g.H);
+    return wmr_for_length(g.W, "row", [&](auto mx) {
+        using MX = decltype(mx);
+        return launch_rows<MX>(&k_wmr_rows_out<MX>, nframes * qpf, st, T, Pt, autocorr, psd, twx, peak, g, nframes, qpf, psd_scale, flags);
+    });
+}
+
+int wmr_psd_autocorr(const float* frames, int nframes, int ny, int nx, const float2* twx, const float2* twy, float2* T, float* Pt,
+                     float* scratch, float* psd, float psd_scale, float* autocorr, unsigned flags, hipStream_t st) {
+    const WmrGeom g = wmr_plain_geom(ny, nx);
+    float* pmax = scratch;                       // (nframes, hp): by-product of the shared forward row kernel, unused here
+    float* peak = scratch + (size_t)nframes * g.hp;
+    int rc;
+    if ((rc = wmr_rows_fwd(frames, T, twx, pmax, g, nframes, st))) return rc;
+    if ((rc = wmr_cols_launch<1>(T, nullptr, twy, nullptr, nullptr, g, nframes, psd ? Pt : nullptr, flags, autocorr ? 1 : 0, st))) return rc;
+    if (autocorr && (flags & B4D_NORM_PEAK)) {
+        hipLaunchKernelGGL(k_wmr_peak, dim3(nframes), dim3(256), 0, st, (const float2*)T, g, peak);
+        B4D_HIP(hipGetLastError());
+    }
+    return wmr_rows_out(T, Pt, autocorr, psd, twx, peak, g, nframes, psd_scale, flags, st);
+}
+
+int wmr_rows_inv(const float2* T, float* out, const float2* twx, const float* amax, const WmrGeom& g, int nframes, hipStream_t st) {
+    const int qpf = wmr_quads_per_frame(g.H);
+    return wmr_for_length(g.W, "row", [&](auto mx) {
+        using MX = decltype(mx);
+        return launch_rows<MX>(&k_wmr_rows_inv<MX>, nframes * qpf, st, T, out, twx, amax, g, nframes, qpf);
+    });
+}
+
+// ---- general-size correlation on the same passes (b4d_track.hip, b4d_general.hip) -----------------------------------------
 size_t wmr_spectrum_elems(int ny, int nx) { return (size_t)(nx / 2 + 1) * wmr_pitch(ny); }
 
 int wmr_forward_spectra(const float* frames, int nframes, int ny, int nx, const float2* twx, const float2* twy, float2* S, float* scratch,
@@ -980,65 +962,28 @@ int wmr_product_inverse(const float2* A, const float2* B, const int* ia, const i
                         float2* G, int whiten, float eps, unsigned flags, hipStream_t st) {
     const WmrGeom g = wmr_plain_geom(ny, nx);
     const unsigned grid = (unsigned)npairs * (unsigned)g.Wh;
-    switch (g.H) {
-#define X(N_, A_, B_, C_, L_)                                                                                                            \
-    case N_:                                                                                                                             \
-        if (whiten)                                                                                                                      \
-            hipLaunchKernelGGL((k_wmr_cols_prod<Mix3<A_, B_, C_, L_>, true>), dim3(grid), dim3(L_), 0, st, A, B, ia, ib, G, twy, g, eps, flags);  \
-        else                                                                                                                             \
-            hipLaunchKernelGGL((k_wmr_cols_prod<Mix3<A_, B_, C_, L_>, false>), dim3(grid), dim3(L_), 0, st, A, B, ia, ib, G, twy, g, eps, flags); \
-        break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix column kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return wmr_for_length(g.H, "column", [&](auto my) {
+        using MY = decltype(my);
+        auto kernel = whiten ? &k_wmr_cols_prod<MY, true> : &k_wmr_cols_prod<MY, false>;
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(MY::LANES), 0, st, A, B, ia, ib, G, twy, g, eps, flags);
+        B4D_HIP(hipGetLastError());
+        return (int)B4D_OK;
+    });
 }
-
-int wmr_quads_per_frame(int ny) { return ((ny + 1) / 2 + WMR_Q - 1) / WMR_Q; }
 
 int wmr_rows_magnitude(const float2* G, int npairs, int ny, int nx, const float2* twx, float* mag, float* part_val, int* part_idx,
                        unsigned* selw, int sel_stride, unsigned pred_bin, float* compact, hipStream_t st) {
     const WmrGeom g = wmr_plain_geom(ny, nx);
-    const int qpf = wmr_quads_per_frame(ny), nquads = npairs * qpf;
-    size_t lds = 0;
-    int grid = 0, rc;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                       \
-    case N_: {                                                                                                                      \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                            \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_mag<MX>, nquads, st, &lds, &grid))) return rc;                                   \
-        hipLaunchKernelGGL((k_wmr_rows_mag<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, G, mag, part_val, part_idx, twx, g, npairs, qpf, \
-                           selw, sel_stride, pred_bin, compact);                                                                    \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    const int qpf = wmr_quads_per_frame(ny);
+    return wmr_for_length(g.W, "row", [&](auto mx) {
+        using MX = decltype(mx);
+        return launch_rows<MX>(&k_wmr_rows_mag<MX>, npairs * qpf, st, G, mag, part_val, part_idx, twx, g, npairs, qpf, selw, sel_stride,
+                               pred_bin, compact);
+    });
 }
 
 int wmr_rows_real_out(const float2* G, int nframes, int ny, int nx, const float2* twx, float* out, hipStream_t st) {
-    const WmrGeom g = wmr_plain_geom(ny, nx);
-    const int qpf = wmr_quads_per_frame(ny), nquads = nframes * qpf;
-    size_t lds = 0;
-    int grid = 0, rc;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                             \
-    case N_: {                                                                                                                            \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                                  \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_out<MX>, nquads, st, &lds, &grid))) return rc;                                         \
-        hipLaunchKernelGGL((k_wmr_rows_out<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, G, (const float*)nullptr, out, (float*)nullptr,    \
-                           twx, (const float*)nullptr, g, nframes, qpf, 1.0f, 0u);                                                        \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return wmr_rows_out(G, nullptr, out, nullptr, twx, nullptr, wmr_plain_geom(ny, nx), nframes, 1.0f, 0u, st);
 }
 
 int wmr_fft2d(const float* frames, int nframes, int ny, int nx, const float2* twx, const float2* twy, float2* S, float* scratch,
@@ -1046,22 +991,11 @@ int wmr_fft2d(const float* frames, int nframes, int ny, int nx, const float2* tw
     int rc = wmr_forward_spectra(frames, nframes, ny, nx, twx, twy, S, scratch, st);
     if (rc) return rc;
     const WmrGeom g = wmr_plain_geom(ny, nx);
-    const int qpf = wmr_quads_per_frame(ny), nquads = nframes * qpf;
-    size_t lds = 0;
-    int grid = 0;
-    switch (g.W) {
-#define X(N_, A_, B_, C_, L_)                                                                                                  \
-    case N_: {                                                                                                                 \
-        using MX = Mix3<A_, B_, C_, L_>;                                                                                       \
-        if ((rc = wmr_rows_launch<MX>(&k_wmr_rows_spec<MX>, nquads, st, &lds, &grid))) return rc;                             \
-        hipLaunchKernelGGL((k_wmr_rows_spec<MX>), dim3(grid), dim3(WMR_Q* L_), lds, st, (const float2*)S, out, g, nframes, qpf); \
-    } break;
-        B4D_WMR_LENGTHS(X)
-#undef X
-        default: return fail(B4D_ESIZE, "no mixed-radix row kernel for this length");
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    const int qpf = wmr_quads_per_frame(ny);
+    return wmr_for_length(g.W, "row", [&](auto mx) {
+        using MX = decltype(mx);
+        return launch_rows<MX>(&k_wmr_rows_spec<MX>, nframes * qpf, st, (const float2*)S, out, g, nframes, qpf);
+    });
 }
 
 }  // namespace b4d

@@ -266,6 +266,26 @@ def test_general_lengths_vs_oracle(gs, shape):
     assert ac[shape[0] // 2, shape[1] // 2] == 1.0 and int(np.argmax(ac)) == (shape[0] // 2) * shape[1] + shape[1] // 2
 
 
+@pytest.mark.parametrize("shape", [(228, 228), (171, 170), (170, 228)])
+def test_general_length_stacks_walk_every_quad(gs, shape):
+    """Three-frame stacks on the mixed-radix route at the row counts where its persistent quad loop can go wrong: 228 rows are
+    114 pairs = 29 quads per frame, an odd count, so the even-padded quad numbering holds invalid items between the frames;
+    170 and 171 rows end in a quad with one active pair, and 171 in a pair without a second row.  Every frame of the stack
+    equals the single-frame call bit for bit, and frame 0 meets the oracle."""
+    from oracle import signal_np as S
+
+    rng = np.random.default_rng(shape[0] * 31 + shape[1])
+    st = (rng.poisson(200.0, size=(3,) + shape) + 5 * rng.random((3,) + shape)).astype(np.float32)
+    f3 = gs.fft2d_stack(st)
+    p3 = gs.psd2d_stack(st)
+    for i in range(3):
+        assert np.array_equal(f3[i], gs.fft2d(st[i])[0])
+        assert np.array_equal(p3[i], gs.psd2d(st[i])[0])
+    r64 = st[0].astype(np.float64)
+    assert nerr(f3[0], S.fft2d(r64)[0]) < TOL
+    assert nerr(p3[0], S.psd2d(r64)[0]) < TOL
+
+
 @pytest.mark.parametrize("shape", [(600, 600), (720, 1280), (1000, 2048), (513, 300), (2160, 2560), (264, 520), (520, 264)])
 def test_large_general_lengths_vs_oracle(gs, shape):
     """Sides beyond the DFT-matrix range that split as 2^k * A * B (detector formats such as 2560 x 2160): fused

@@ -266,6 +266,30 @@ def test_phase_correlation_general_sizes(gs, shape, observe):
         observe("general_sizes/snr_rel", _rel(got[3], want[3]), BARS["general_sizes/snr_rel"])
 
 
+def test_phase_correlation_batch_228(gs, observe):
+    """Four pairs in one call at 228 x 228 (mixed-radix route; 29 quads per map, an odd count, so the row kernels' even-padded
+    quad numbering holds invalid items between the maps): every pair against the oracle."""
+    from oracle import signal_np as S
+
+    H = W = 228
+    rng = np.random.default_rng(228)
+    base = synth_frame(256, 5)[:H, :W]
+    shifts = [(0, 0), (3, -5), (-7, 11), (6, 2)]
+    stack = np.stack([(np.roll(base, s, axis=(0, 1)) + rng.normal(size=(H, W)) * 20) for s in shifts]).astype(np.float32)
+    roi = (70, 131, 90, 151)
+    sl = (slice(roi[0], roi[1]), slice(roi[2], roi[3]))
+    res, pij = gs.phase_correlation_batch(stack, stack, [0], [roi], [0, 1, 2, 3], [0, 0, 0, 0], return_peak_ij=True)
+    assert res.shape == (4, 4)
+    for i, (dy, dx) in enumerate(shifts):
+        want = S.phase_correlation(stack[0][sl], stack[i], slices_yx=sl)
+        mag = S.phase_correlation_map(stack[0][sl], stack[i], slices_yx=sl)
+        assert (pij[i, 0], pij[i, 1]) == np.unravel_index(np.argmax(mag), mag.shape)   # index output: bit exact
+        assert (round(res[i, 0]), round(res[i, 1])) == (dy, dx)
+        observe("general_sizes/sub_px", max(abs(res[i, 0] - want[0]), abs(res[i, 1] - want[1])), BARS["general_sizes/sub_px"])
+        observe("general_sizes/peak_rel", _rel(res[i, 2], want[2]), BARS["general_sizes/peak_rel"])
+        observe("general_sizes/snr_rel", _rel(res[i, 3], want[3]), BARS["general_sizes/snr_rel"])
+
+
 @pytest.mark.parametrize("shape", [(64, 64), (128, 256), (2048, 512), (512, 2048), (2048, 2048), (4096, 1024),
                                    (600, 720), (1080, 1920), (767, 1024), (1024, 768)])   # the last four: mixed-radix kernels (767: fused route)
 def test_phase_correlation_power_of_two_sizes_all_routes(gs, shape, observe):

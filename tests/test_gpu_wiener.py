@@ -211,6 +211,24 @@ def test_mixed_radix_route_special_values(pp):
         assert float(np.max(np.abs(got[t] - ref))) < 2e-5 * float(stack[t].max())
 
 
+def test_mixed_radix_route_stack_equals_frames(pp):
+    """Three frames in one call on the three-kernel route, padded 264 x 520 (33 quads per frame: an odd count, so the row
+    kernels' even-padded quad numbering holds invalid items between the frames): every frame equals its single-frame call bit
+    for bit, and frame 0 meets the oracle."""
+    from barc4dip_amd.preprocessing import filters
+    from oracle import wiener_np as W
+
+    ky, kx = filters._gaussian_psf(1.5, 1.5).shape
+    assert (256 + 2 * (ky // 2), 512 + 2 * (kx // 2)) == (264, 520)
+    base = synth.speckle_frame(512, 13)[:256, :512]
+    st = np.ascontiguousarray(np.stack([base, base[::-1], base[:, ::-1] * 0.5 + 3.0]), dtype=np.float32)
+    out = pp.deconvolve_psf(st, sigma=1.5)
+    for i in range(3):
+        assert np.array_equal(out[i], pp.deconvolve_psf(st[i], sigma=1.5))
+    ref = W.deconvolve_psf(st[0], sigma=1.5)
+    assert float(np.max(np.abs(out[0] - ref))) < 2e-5 * float(np.max(np.abs(st[0])))
+
+
 def test_stack_balance_and_errors(pp):
     from oracle import wiener_np as W
 
