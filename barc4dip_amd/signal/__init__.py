@@ -1,11 +1,12 @@
 """GPU drop-in for ``barc4dip.signal`` (same public names as signal/__init__.py:6-26)."""
 from __future__ import annotations
 
-from . import corr, displacement, fft, tracking
+from . import corr, displacement, fft, tracking, wavefront
 from .corr import autocorr2d, autocorr2d_stack, psd_autocorr2d_stack, xcorr2d
 from .displacement import displacement_grid, displacement_map
 from .tracking import (phase_correlation, phase_correlation_batch, template_matching, template_matching_batch,
                        track_translation)
+from .wavefront import integrate_gradient, wavefront_from_displacement
 from .fft import fft1d, fft2d, fft2d_stack, freq_axes2d, freq_axis1d, psd1d, psd2d, psd2d_stack
 
 __all__ = [
@@ -14,4 +15,5 @@ __all__ = [
     "freq_axis1d", "freq_axes2d", "fft1d", "fft2d", "psd1d", "psd2d", "xcorr2d", "autocorr2d",
     "fft2d_stack", "psd2d_stack", "autocorr2d_stack", "psd_autocorr2d_stack",
     "displacement", "displacement_map", "displacement_grid",
+    "wavefront", "integrate_gradient", "wavefront_from_displacement",
 ]

@@ -305,6 +305,28 @@ int b4d_uw_step(const void* y, const void* tf, const float* areg2, void* x_sampl
                 const float* r2, unsigned long long seed, int sweep, int burnin, float gn, float gx, int ny, int nxh,
                 double* sums4, void* stream);
 
+/* Wavefront reconstruction (barc4dip_amd/signal/wavefront.py; no counterpart in the reference, which stops at the shift map).
+ * b4d_integrate_gradient: least-squares integration of the slope fields gy = d phi / dy, gx = d phi / dx given on the nodes of a
+ *   regular (ny, nx) grid with spacings hy, hx > 0, in Southwell geometry: the slope on the edge between two neighbouring nodes
+ *   is the mean of the two node slopes, and phi is the zero-mean minimiser of
+ *     sum ((phi[i+1][j] - phi[i][j]) / hy - gbar_y[i][j])^2 + sum ((phi[i][j+1] - phi[i][j]) / hx - gbar_x[i][j])^2.
+ *   Solved exactly through the orthonormal DCT-II, which diagonalises the 5-point Neumann Laplacian of the normal equations:
+ *   one elementwise launch for the right-hand side and four float32 matrix products on the matrix cores for the whole batch.
+ *   gy, gx, out: DEVICE (n, ny, nx) float32, out distinct from gy and gx; workspace: DEVICE, b4d_integrate_workspace_bytes(n, ny, nx)
+ *   bytes (0 for an unsupported shape).  Sides 1 .. 2048 (B4D_ESIZE beyond), n <= 65535.  Non-finite input propagates.
+ *   Asynchronous on `stream`; the DCT basis of a side is built on first use (float64 on the host, a blocking upload) and cached.
+ * b4d_poly2_fit: least-squares fit of c0 + c1 u + c2 v + c3 u^2 + c4 u v + c5 v^2 to every map w (n, ny, nx), with
+ *   u = (j - (nx-1)/2) / max((nx-1)/2, 1) along x and v likewise along y (both in [-1, 1]); float64 moments on the device, the
+ *   inverse Gram matrix of the grid from the host.  A term that a side of 1 or 2 nodes cannot tell from the earlier ones gets 0.
+ *   coeff: DEVICE (n, 6) float64.  residual (DEVICE (n, ny, nx) float32, may be w itself) and rms (DEVICE (n) float64) are
+ *   optional, both or neither: residual = scale * (w - the terms whose bit is set in remove_mask, bit k for c_k), rms = its
+ *   population standard deviation.  Asynchronous on `stream`. */
+size_t b4d_integrate_workspace_bytes(int n, int ny, int nx);
+int b4d_integrate_gradient(const float* gy, const float* gx, int n, int ny, int nx, double hy, double hx, void* workspace,
+                           float* out, void* stream);
+int b4d_poly2_fit(const float* w, int n, int ny, int nx, unsigned remove_mask, double scale, double* coeff, float* residual,
+                  double* rms, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
