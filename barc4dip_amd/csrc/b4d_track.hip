@@ -222,6 +222,13 @@ struct FinArgs {
 // peak quality + Taylor step of one pair (one lane), op for op like tracking.py:314-375 (float32 scalars, no contraction)
 __device__ inline void track_finish(const FinArgs& p, size_t pair, const float* __restrict__ mag, int mny, int mnx, int oy, int ox,
                                     float bv, int bi, float med) {
+    // The arg-max sentinel survives every merge only when no element of the map compared greater than it: magnitudes are >= 0 and
+    // NCC responses >= -1, so the map is NaN everywhere (one non-finite pixel does that to a whitened map).  NumPy's arg-max of
+    // such a map is its first element, and peak and snr are NaN (tracking.py:283-290 on an all-NaN `corr`).
+    if (bi == 0x7fffffff) {
+        bi = 0;
+        bv = __builtin_nanf("");
+    }
     const int mi = bi / mnx, mj = bi % mnx;
     auto c = [&](int di, int dj) { return mag[(size_t)(mi + di) * mnx + (mj + dj)]; };
     peak_finish(c, mi, mj, mny, mnx, oy, ox, bv, med, p.subpixel, p.eps, p.out + pair * 4);
@@ -279,7 +286,11 @@ __global__ void __launch_bounds__(1024) k_track_fin(FinArgs p) {
     const float* cx = msrc;
     float* comp = p.compact ? p.compact + pair * stride : nullptr;
     float med;
-    if (n & 1u) {
+    if (bi == 0x7fffffff) {
+        // all-NaN map (uniform: every lane holds the merged sentinel): there is no element to rank -- radix_select would leave its
+        // bin words unwritten and continue on a gathered array of undefined length -- and the median is NaN like np.median's
+        med = __builtin_nanf("");
+    } else if (n & 1u) {
         med = key2f(radix_select<REP>(msrc, n, n / 2, hist, sh, nl, ne, comp));
     } else {
         const unsigned ka = radix_select<REP>(msrc, n, n / 2 - 1, hist, sh, nl, ne, comp, &cx, &cn);
@@ -813,13 +824,15 @@ __global__ void __launch_bounds__(256) k_embed_roi(const float* __restrict__ fra
     canvas[(size_t)blockIdx.y * ny * nx + e] = in ? (frames[(size_t)sd.frame * ny * nx + e] - sd.mean) / sd.denom : 0.f;
 }
 
-// whitened cross-power spectra of `pairs` (image, template) spectrum pairs.  grid (ceil(npix/256), pairs)
+// whitened cross-power spectra of `pairs` (image, template) spectrum pairs, DC bin zeroed.  grid (ceil(npix/256), pairs)
 __global__ void __launch_bounds__(256) k_gen_cps(const float2* __restrict__ spec, const int* __restrict__ ia, const int* __restrict__ ib,
                                                  int npix, float eps, float2* __restrict__ out) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= npix) return;
+    // DC bin: the product of two z-scored frames' sums is a rounded zero, 0 after whitening in the float64 protocol (b4d_phase_correlation)
     out[(size_t)blockIdx.y * npix + e] =
-        cross_power<true>(spec[(size_t)ia[blockIdx.y] * npix + e], spec[(size_t)ib[blockIdx.y] * npix + e], eps);
+        e == 0 ? make_float2(0.f, 0.f)
+               : cross_power<true>(spec[(size_t)ia[blockIdx.y] * npix + e], spec[(size_t)ib[blockIdx.y] * npix + e], eps);
 }
 
 // mag = |Re(R)| * scale, fftshift-ed (signal/tracking.py:283-285; the imaginary part of the Hermitian inverse is rounding
@@ -1077,7 +1090,7 @@ static int wmr_phase_correlation(b4d_plan* pl, const float* images, int nimg, co
     }
     for (int p0 = 0; p0 < npairs; p0 += pc) {
         const int np = std::min(pc, npairs - p0);
-        if ((rc = wmr_product_inverse(spec, spec, pidx + p0, pidx + npairs + p0, np, ny, nx, pl->tw_y, G, 1, (float)eps, 0u, st))) return rc;
+        if ((rc = wmr_product_inverse(spec, spec, pidx + p0, pidx + npairs + p0, np, ny, nx, pl->tw_y, G, 1, (float)eps, B4D_REMOVE_MEAN, st))) return rc;
         const unsigned pred = predicted_median_bin(npix, predict_mode);
         B4D_HIP(hipMemsetAsync(msel, 0, sizeof(SelState) * (size_t)pc, st));
         if ((rc = wmr_rows_magnitude(G, np, ny, nx, pl->tw_x, mag, pval, pind, reinterpret_cast<unsigned*>(msel), SEL_WORDS, pred, medws, st)))
@@ -1341,8 +1354,11 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
         float* pval = pval0 + (size_t)2048 * pc * slot;
         int* pind = pind0 + (size_t)2048 * pc * slot;
         SelState* msel = msel0 + (size_t)pc * slot;
+        // B4D_REMOVE_MEAN: both operands are z-scored, so the DC bin of their product is a rounded zero.  In float64 (the reference's
+        // protocol) |prod| there is far below eps and the whitened bin is 0; in float32 it is of the order of eps and the bin would keep
+        // an arbitrary modulus in [0, 1], i.e. add a constant up to 1 / N to the whole map (the median of a delta-like map is nothing else)
         if ((rc = product_inverse<true>(pl, spec, nyq, pidx + p0, pidx + npairs + p0, spec, nyq, np, g, gnyq, (float)eps,
-                                        0u, ls, srcs)))
+                                        B4D_REMOVE_MEAN, ls, srcs)))
             return rc;
         RowOutArgs ra{};
         ra.g = g;

@@ -76,3 +76,76 @@ def speckle_stack_device(t: int, n: int, *, seed0: int = 1234, device="cuda", ch
         inten *= mean / inten.mean(dim=(1, 2), keepdim=True)
         out[a:b] = torch.poisson(inten, generator=g)
     return out
+
+
+# ---- white speckle for tracker edge tests ------------------------------------------------------------------------------------
+# `speckle_frame` has a correlation length of several pixels (pupil_div): on crops of 64 ... 128 rows a 21 ... 41-px template is
+# lost in the noise of the whitened phase-correlation map.  White, fully developed speckle (exponential intensity statistics, no
+# spatial correlation) keeps every spectral bin informative, so small templates still give one dominant peak at ANY cyclic shift.
+
+def white_speckle_pairs(shape, shifts, *, seed: int, noise: float = 10.0, dtype=np.float32):
+    """(base (H, W), stack (len(shifts), H, W)): base = Gamma(1, 100) intensities, frame i = roll(base, shifts[i]) + N(0, noise)."""
+    H, W = shape
+    rng = np.random.default_rng(seed)
+    base = rng.gamma(1.0, 100.0, (H, W)).astype(dtype)
+    stack = np.empty((len(shifts), H, W), dtype=dtype)
+    for i, (dy, dx) in enumerate(shifts):
+        stack[i] = np.roll(base, (int(dy), int(dx)), axis=(0, 1)) + rng.normal(0.0, noise, (H, W))
+    return base, stack
+
+
+def edge_shift_sweep(H: int, W: int):
+    """54 cyclic shifts whose correlation peak lies on the first / last row or column of the fftshift-ed (H, W) map, next to them,
+    and on both sides of the zero-shift seam of the unshifted map (dy, dx in {-1, 0})."""
+    dys = (-(H // 2), -(H // 2) + 1, -2, -1, 0, 1, 2, H - H // 2 - 2, H - H // 2 - 1)
+    dxs = (-(W // 2), -(W // 2) + 1, -1, 0, 1, W - W // 2 - 1)
+    return [(dy, dx) for dy in dys for dx in dxs]
+
+
+def edge_roi(shape, tpl_hw):
+    """(y0, y1, x0, x1) of the template ROI used by the tracker edge tests: off-centre by (-3, +2)."""
+    (H, W), (h, w) = shape, tpl_hw
+    y0, x0 = (H - h) // 2 - 3, (W - w) // 2 + 2
+    return y0, y0 + h, x0, x0 + w
+
+
+# (frame shape, template shape, transform route of b4d_phase_correlation) of the tracker edge tests
+TRACKING_EDGE_CASES = (
+    ((64, 64), (31, 31), "pow2"),        # one workgroup recomputes the three row pairs around the peak, 32 pairs per workgroup
+    ((64, 128), (31, 41), "pow2"),       # nx != ny
+    ((128, 512), (41, 61), "pow2"),      # 8 row pairs per workgroup
+    ((64, 2048), (31, 121), "pow2"),     # two workgroups for the three row pairs
+    ((64, 4096), (31, 121), "pow2"),     # three
+    ((100, 37), (41, 21), "dft"),        # DFT-matrix route, odd width
+    ((171, 170), (61, 61), "dft"),
+    ((228, 228), (61, 61), "mixed"),     # mixed-radix, odd quad count
+    ((264, 520), (61, 81), "mixed"),     # mixed-radix, fused
+)
+
+
+def degenerate_tracking_inputs(shape, tpl_hw, *, seed: int):
+    """name -> (template source frame, image, roi) of inputs whose phase-correlation map is all-zero ("const_*", "tpl_1x1"),
+    all-NaN ("nan_*", "inf_image"), delta-like ("whole_frame") or without a dominant peak ("one_row")."""
+    H, W = shape
+    base, stack = white_speckle_pairs(shape, [(1, 2), (3, -2)], seed=seed)
+    frame = stack[0]
+    roi = edge_roi(shape, tpl_hw)
+    y0, y1, x0, x1 = roi
+
+    def poke(a, y, x, v):
+        a = a.copy()
+        a[y, x] = v
+        return a
+
+    flat_tpl = base.copy()
+    flat_tpl[y0:y1, x0:x1] = 7.0
+    return {
+        "const_image": (base, np.full(shape, 7.0, np.float32), roi),
+        "const_template": (flat_tpl, frame, roi),
+        "tpl_1x1": (base, frame, (y0, y0 + 1, x0, x0 + 1)),
+        "nan_image": (base, poke(frame, 5, 7, np.nan), roi),
+        "nan_template": (poke(base, y0 + 4, x0 + 9, np.nan), frame, roi),
+        "inf_image": (base, poke(frame, 5, 7, np.inf), roi),
+        "whole_frame": (base, np.roll(base, (3, -2), axis=(0, 1)), (0, H, 0, W)),
+        "one_row": (base, frame, edge_roi(shape, (1, 31))),
+    }
