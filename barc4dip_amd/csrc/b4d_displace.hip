@@ -239,6 +239,7 @@ __global__ void __launch_bounds__(DM_THREADS) k_displace(DispArgs a) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int k = tid; k < nm; k += nthr) argmax_merge(bv, bi, M[k], k);
+    // (block_argmax of b4d_peak.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_down(bv, o, 64);

@@ -1,13 +1,20 @@
-// b4d_track.hip -- cross-correlation and phase-correlation translation tracking on gfx950
-// (reference signal/corr.py:169-253, signal/tracking.py:191-375).
+// b4d_track.hip -- cross-correlation, phase-correlation translation tracking and NCC template matching on gfx950
+// (reference signal/corr.py:169-253, signal/tracking.py:81-375).
 //
 // One 2-D forward transform per distinct image and per distinct template (K1 with ROI/z-score
 // sources + forward column pass), then per (image, template) pair:
 //   k_col_prod   Fi * conj(Ft) [/(|.| + eps) for phase correlation] fused into the inverse column FFT
-//   k_row_c2r    inverse row FFT -> real map (xcorr) or |map| + arg-max partials (tracking)
-//   k_track_fin  first-occurrence arg-max, exact median by 3-pass radix select, 3x3 Taylor step
+//   k_row_c2r    inverse row FFT -> real map (xcorr, NCC numerator) or |map| + arg-max partials (tracking)
+//   k_ncc_map    template matching: the normalised map, |map| and arg-max partials from the numerator and window sums
+//   epilogue     first-occurrence arg-max, exact median by radix select, 3x3 Taylor step: k_track_fin (three passes on the
+//                map) or, where the map kernel has counted and gathered the expected median bin, k_track_select (verdict per
+//                pair) + k_track_fin2 (passes 2-3 on the bin) with k_track_fin behind it for the pairs left over.  The two
+//                share fin_map, fin_argmax (block_argmax, b4d_peak.hpp), median_from_select and track_finish.
 // Image spectra are computed once and reused by every template (the reference re-transforms
 // the same frame 18 times per time step, metrics/speckles.py:347-415).
+// Three phase-correlation routes (power-of-two, mixed-radix, DFT-matrix) and template matching share the host side: the
+// workspace of an entry point is ONE layout run twice (track_workspace), the sources are validated, uploaded and z-scored by
+// track_sources, and every kernel goes through launch().
 #include <cstring>
 
 #include "b4d_fft2d.hpp"
@@ -16,6 +23,17 @@
 #include "b4d_wiener_mr.hpp"
 
 namespace b4d {
+
+// Every launch of this unit: the dynamic-LDS attribute where the kernel uses dynamic LDS (ensure_dynamic_lds, b4d_common.hpp),
+// the launch, and its one error check.  The arguments are converted to the kernel's own parameter types.
+template <class... P, class... A>
+static int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    if (lds)
+        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
 
 // ------------------------------------------------------------------------------------ ROI statistics
 // Population mean / std of every ROI in float64, stored as float like NumPy's float32 arithmetic does:
@@ -27,12 +45,11 @@ __global__ void __launch_bounds__(256) k_roi_part(const float* __restrict__ fram
                                                   double* __restrict__ part) {
     __shared__ double sh[8];
     const RowSrc sd = srcs[blockIdx.y];
-    const int h = sd.y1 - sd.y0, w = sd.x1 - sd.x0, n = h * w;
+    const int h = sd.y1 - sd.y0, w = sd.x1 - sd.x0;
     const float* f = frames + (size_t)sd.frame * ny * nx;
     const double x0 = (double)f[(size_t)sd.y0 * nx + sd.x0];
     // a slice = a range of ROI rows, walked row by row: no division per pixel (the flat-index form cost a full-frame source,
     // 5.5 M pixels at 2160 x 2560, 160 us: a quarter of a small general-size tracking call), four rows in flight per lane
-    (void)n;
     const int per = (h + ROI_SPLIT - 1) / ROI_SPLIT, r0 = blockIdx.x * per, r1 = min(h, r0 + per);
     double a1 = 0.0, a2 = 0.0;
     const float* base = f + (size_t)sd.y0 * nx + sd.x0;
@@ -93,10 +110,8 @@ __global__ void __launch_bounds__(64) k_roi_fin(const float* __restrict__ frames
 }
 
 static int roi_stats(const float* frames, int ny, int nx, double eps, RowSrc* srcs, int items, double* part, hipStream_t st) {
-    hipLaunchKernelGGL(k_roi_part, dim3(ROI_SPLIT, items), dim3(256), 0, st, frames, ny, nx, srcs, part);
-    hipLaunchKernelGGL(k_roi_fin, dim3((items + 63) / 64), dim3(64), 0, st, frames, ny, nx, eps, items, part, srcs);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    if (const int rc = launch(k_roi_part, dim3(ROI_SPLIT, items), dim3(256), 0, st, frames, ny, nx, srcs, part)) return rc;
+    return launch(k_roi_fin, dim3((items + 63) / 64), dim3(64), 0, st, frames, ny, nx, eps, items, part, srcs);
 }
 
 // ------------------------------------------------------------------------------------ product + inverse column pass
@@ -219,9 +234,67 @@ struct FinArgs {
     int skip_stride;
 };
 
+// the map of one pair as the epilogue sees it
+struct FinMap {
+    int mny, mnx, oy, ox;   // rows, columns, origin the shifts are counted from
+    unsigned n;             // mny * mnx
+    size_t stride;          // elements between the maps (and the median scratch) of consecutive pairs
+    const float* mag;       // the map
+    const float* msrc;      // what the median runs over
+};
+__device__ __forceinline__ FinMap fin_map(const FinArgs& p, size_t pair) {
+    FinMap m;
+    m.mny = p.ny, m.mnx = p.nx, m.oy = p.ny / 2, m.ox = p.nx / 2;
+    if (p.geom) {   // template matching: compact (rows, columns) maps, shifts counted from the template's position
+        m.mny = p.geom[4 * pair];
+        m.mnx = p.geom[4 * pair + 1];
+        m.oy = p.geom[4 * pair + 2];
+        m.ox = p.geom[4 * pair + 3];
+    }
+    m.n = (unsigned)m.mny * m.mnx;
+    m.stride = p.stride ? p.stride : (size_t)m.n;
+    m.mag = p.mag + pair * m.stride;
+    m.msrc = p.med_src ? p.med_src + pair * m.stride : m.mag;
+    return m;
+}
+
+// arg-max of one pair over its per-workgroup partials (first occurrence in row-major order), in every lane; whole workgroup of
+// 1024 lanes, sv / si: 16 LDS words each
+__device__ __forceinline__ void fin_argmax(const FinArgs& p, size_t pair, float& bv, int& bi, float* sv, int* si) {
+    bv = -INFINITY;
+    bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < p.nblk; i += blockDim.x)
+        argmax_merge(bv, bi, p.part_val[pair * p.nblk + i], p.part_idx[pair * p.nblk + i]);
+    block_argmax(bv, bi, sv, si, 16);
+    __syncthreads();
+}
+
+// rank of the middle element of n (the lower one of the two when n is even)
+__device__ __forceinline__ unsigned lower_middle(unsigned n) { return (n & 1u) ? n / 2 : n / 2 - 1; }
+
+// np.median of an n-element float32 map (mean of the two middle values for even counts, evaluated in float32 like NumPy does
+// for a float32 array) from the result of radix_select for rank lower_middle(n): its key `ka`, n_less, n_equal and the array
+// (cx, cn) the select ended on (the gathered bin, or the map).  The upper middle value of an even count is the next larger
+// element: in (cx, cn), else (rare) anywhere above it in the whole map `full`.  Returns false (uniformly) when that second
+// search is needed and `full` is null.  Whole workgroup; hist: 16 LDS words.
+__device__ inline bool median_from_select(unsigned ka, unsigned n, unsigned nl, unsigned ne, const float* cx, unsigned cn,
+                                          const float* full, unsigned* hist, float& med) {
+    const float a = key2f(ka);
+    float b = a;
+    if (!(n & 1u) && nl + ne <= n / 2) {
+        unsigned kb = next_larger_key(cx, cn, ka, hist);
+        if (kb == 0xffffffffu && cx != full) {
+            if (!full) return false;
+            kb = next_larger_key(full, n, ka, hist);
+        }
+        b = key2f(kb);
+    }
+    med = (n & 1u) ? a : __fmul_rn(__fadd_rn(a, b), 0.5f);
+    return true;
+}
+
 // peak quality + Taylor step of one pair (one lane), op for op like tracking.py:314-375 (float32 scalars, no contraction)
-__device__ inline void track_finish(const FinArgs& p, size_t pair, const float* __restrict__ mag, int mny, int mnx, int oy, int ox,
-                                    float bv, int bi, float med) {
+__device__ inline void track_finish(const FinArgs& p, size_t pair, const FinMap& m, float bv, int bi, float med) {
     // The arg-max sentinel survives every merge only when no element of the map compared greater than it: magnitudes are >= 0 and
     // NCC responses >= -1, so the map is NaN everywhere (one non-finite pixel does that to a whitened map).  NumPy's arg-max of
     // such a map is its first element, and peak and snr are NaN (tracking.py:283-290 on an all-NaN `corr`).
@@ -229,99 +302,51 @@ __device__ inline void track_finish(const FinArgs& p, size_t pair, const float* 
         bi = 0;
         bv = __builtin_nanf("");
     }
-    const int mi = bi / mnx, mj = bi % mnx;
-    auto c = [&](int di, int dj) { return mag[(size_t)(mi + di) * mnx + (mj + dj)]; };
-    peak_finish(c, mi, mj, mny, mnx, oy, ox, bv, med, p.subpixel, p.eps, p.out + pair * 4);
+    const int mi = bi / m.mnx, mj = bi % m.mnx;
+    auto c = [&](int di, int dj) { return m.mag[(size_t)(mi + di) * m.mnx + (mj + dj)]; };
+    peak_finish(c, mi, mj, m.mny, m.mnx, m.oy, m.ox, bv, med, p.subpixel, p.eps, p.out + pair * 4);
     if (p.peak_ij) {
         p.peak_ij[pair * 2] = mi;
         p.peak_ij[pair * 2 + 1] = mj;
     }
 }
 
-// grid (pairs), block 1024, dynamic LDS FIN_LDS bytes
+// The whole select on the map.  grid (pairs), block 1024, dynamic LDS FIN_LDS bytes
 constexpr int FIN_REP = 4;
 constexpr size_t FIN_LDS = sizeof(unsigned) * 2048 * FIN_REP;
 __global__ void __launch_bounds__(1024) k_track_fin(FinArgs p) {
-    constexpr int REP = FIN_REP;
     extern __shared__ unsigned hist[];   // FIN_REP copies of the 2048-bin histogram
     __shared__ unsigned sh[4];
     __shared__ float sv[16];
     __shared__ int si[16];
     const size_t pair = blockIdx.x;
     if (p.skip && p.skip[pair * p.skip_stride]) return;
-    int mny = p.ny, mnx = p.nx, oy = p.ny / 2, ox = p.nx / 2;
-    if (p.geom) {
-        mny = p.geom[4 * pair];
-        mnx = p.geom[4 * pair + 1];
-        oy = p.geom[4 * pair + 2];
-        ox = p.geom[4 * pair + 3];
-    }
-    const unsigned n = (unsigned)mny * mnx;
-    const size_t stride = p.stride ? p.stride : (size_t)n;
-    const float* mag = p.mag + pair * stride;
-    const float* msrc = p.med_src ? p.med_src + pair * stride : mag;
-    // ---- arg-max over the per-workgroup partials (first occurrence in row-major order)
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < p.nblk; i += blockDim.x)
-        argmax_merge(bv, bi, p.part_val[pair * p.nblk + i], p.part_idx[pair * p.nblk + i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_down(bv, o, 64);
-        const int oi = __shfl_down(bi, o, 64);
-        argmax_merge(bv, bi, ov, oi);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sv[threadIdx.x >> 6] = bv;
-        si[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
-    bv = sv[0];
-    bi = si[0];
-    for (int i = 1; i < 16; ++i) argmax_merge(bv, bi, sv[i], si[i]);
-    __syncthreads();
-    // ---- median of the magnitude map (np.median: mean of the two middle values for even counts,
-    //      evaluated in float32 like NumPy does for a float32 array)
-    unsigned nl, ne, cn = n;
-    const float* cx = msrc;
-    float* comp = p.compact ? p.compact + pair * stride : nullptr;
-    float med;
-    if (bi == 0x7fffffff) {
-        // all-NaN map (uniform: every lane holds the merged sentinel): there is no element to rank -- radix_select would leave its
-        // bin words unwritten and continue on a gathered array of undefined length -- and the median is NaN like np.median's
-        med = __builtin_nanf("");
-    } else if (n & 1u) {
-        med = key2f(radix_select<REP>(msrc, n, n / 2, hist, sh, nl, ne, comp));
-    } else {
-        const unsigned ka = radix_select<REP>(msrc, n, n / 2 - 1, hist, sh, nl, ne, comp, &cx, &cn);
-        float a = key2f(ka), b = a;
-        if (nl + ne <= n / 2) {  // upper middle value = next larger element: in the gathered bin, else (rare) anywhere above it
-            unsigned kb = next_larger_key(cx, cn, ka, hist);
-            if (kb == 0xffffffffu && cx != msrc) kb = next_larger_key(msrc, n, ka, hist);
-            b = key2f(kb);
-        }
-        med = __fmul_rn(__fadd_rn(a, b), 0.5f);
+    const FinMap m = fin_map(p, pair);
+    float bv;
+    int bi;
+    fin_argmax(p, pair, bv, bi, sv, si);
+    // all-NaN map (uniform: every lane holds the merged sentinel): there is no element to rank -- radix_select would leave its
+    // bin words unwritten and continue on a gathered array of undefined length -- and the median is NaN like np.median's
+    float med = __builtin_nanf("");
+    if (bi != 0x7fffffff) {
+        unsigned nl, ne, cn;
+        const float* cx;
+        float* comp = p.compact ? p.compact + pair * m.stride : nullptr;
+        const unsigned ka = radix_select<FIN_REP>(m.msrc, m.n, lower_middle(m.n), hist, sh, nl, ne, comp, &cx, &cn);
+        median_from_select(ka, m.n, nl, ne, cx, cn, m.msrc, hist, med);
     }
     if (threadIdx.x != 0) return;
-    track_finish(p, pair, mag, mny, mnx, oy, ox, bv, bi, med);
+    track_finish(p, pair, m, bv, bi, med);
 }
 
-static int launch_track_fin(const FinArgs& fa, int pairs, hipStream_t st) {
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_track_fin), FIN_LDS);
-        if (rc_lds) return rc_lds;
-    }
-    hipLaunchKernelGGL(k_track_fin, dim3(pairs), dim3(1024), FIN_LDS, st, fa);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-
-// ---- phase correlation: the median's first select pass comes from k_row_c2r (one global 2048-bin histogram per pair), the
-// bin's elements are gathered by SEVERAL workgroups per pair (one streamed read of the map over the whole chip), and one
-// workgroup per pair finishes on the gathered ~10 % of the map: passes 2-3 of the select, arg-max partials, Taylor step.
+// ---- The median's first select pass can come from the kernel that writes the map (k_row_c2r, k_wmr_rows_mag, k_ncc_map): it
+// counts the elements below / inside the top-11-bit bin the median is EXPECTED in (one SelState per pair) and gathers the bin's
+// elements by SEVERAL workgroups per pair (one streamed read of the map over the whole chip).  k_track_select then checks
+// the expectation, and one workgroup per pair finishes on the gathered ~10 % of the map: passes 2-3 of the select, arg-max
+// partials, Taylor step (k_track_fin2).
 struct SelState {
     unsigned bin, below, count, fill;   // selected top-11-bit bin, elements under it, elements in it, gather cursor
-    unsigned ok, pad[3];                // the median is in the expected bin: k_row_c2r has already counted and gathered it
+    unsigned ok, pad[3];                // the median is in the expected bin: the map kernel has already counted and gathered it
 };
 constexpr int SEL_WORDS = sizeof(SelState) / sizeof(unsigned);
 
@@ -343,110 +368,65 @@ static unsigned predicted_median_bin(size_t n, int mode) {
 }
 
 // grid (ceil(pairs / 64)), block 64: the expectation holds for pair i when the median's rank falls inside the expected bin
-// (and the gathered count agrees with the counted one)
-__global__ void __launch_bounds__(64) k_track_select(size_t n, SelState* __restrict__ sel, unsigned pred, int pairs) {
+// and the whole bin was gathered.  preds null (phase correlation): every map has n elements and the expected bin is `pred`;
+// else (template matching) pair i has geom[4 i] x geom[4 i + 1] elements and the expected bin preds[i] (k_ncc_sample).
+__global__ void __launch_bounds__(64) k_track_select(SelState* __restrict__ sel, int pairs, unsigned n, unsigned pred,
+                                                     const int* __restrict__ geom, const unsigned* __restrict__ preds) {
     const int pair = blockIdx.x * 64 + threadIdx.x;
     if (pair >= pairs) return;
     SelState* st = sel + pair;
-    const unsigned k = (unsigned)((n & 1u) ? n / 2 : n / 2 - 1);   // rank of the (lower) middle element
+    if (preds) {
+        n = (unsigned)geom[4 * pair] * (unsigned)geom[4 * pair + 1];
+        pred = preds[pair];
+    }
+    const unsigned k = lower_middle(n);
     st->bin = pred;
     st->ok = (pred != 0u && k >= st->below && k < st->below + st->count && st->fill == st->count) ? 1u : 0u;
 }
 
-// grid (pairs), block 1024, dynamic LDS FIN_LDS bytes
+// Passes 2-3 of the select on the gathered bin of the pairs whose expectation held.  grid (pairs), block 1024, dynamic LDS
+// FIN_LDS bytes
 __global__ void __launch_bounds__(1024) k_track_fin2(FinArgs p, SelState* __restrict__ sel) {
-    constexpr int REP = FIN_REP;
     extern __shared__ unsigned hist[];
     __shared__ unsigned sh[4];
     __shared__ float sv[16];
     __shared__ int si[16];
     const size_t pair = blockIdx.x;
     if (!sel[pair].ok) return;    // the expectation failed: k_track_fin does the whole selection on the map
-    int mny = p.ny, mnx = p.nx, oy = p.ny / 2, ox = p.nx / 2;
-    if (p.geom) {   // template matching: compact (rows, columns) maps, shifts counted from the template's position
-        mny = p.geom[4 * pair];
-        mnx = p.geom[4 * pair + 1];
-        oy = p.geom[4 * pair + 2];
-        ox = p.geom[4 * pair + 3];
-    }
-    const unsigned n = (unsigned)mny * mnx;
-    const size_t stride = p.stride ? p.stride : (size_t)n;
-    const float* mag = p.mag + pair * stride;
-    const float* msrc = p.med_src ? p.med_src + pair * stride : mag;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < p.nblk; i += blockDim.x)
-        argmax_merge(bv, bi, p.part_val[pair * p.nblk + i], p.part_idx[pair * p.nblk + i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_down(bv, o, 64);
-        const int oi = __shfl_down(bi, o, 64);
-        argmax_merge(bv, bi, ov, oi);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sv[threadIdx.x >> 6] = bv;
-        si[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
-    bv = sv[0];
-    bi = si[0];
-    for (int i = 1; i < 16; ++i) argmax_merge(bv, bi, sv[i], si[i]);
-    __syncthreads();
-    // ---- median (np.median of a float32 map): passes 2-3 of the select on the gathered bin
+    const FinMap m = fin_map(p, pair);
+    float bv;
+    int bi;
+    fin_argmax(p, pair, bv, bi, sv, si);
     const SelState ss = sel[pair];
-    const float* cx = p.compact + pair * stride;
-    const unsigned cn = ss.count;
+    const float* cx = p.compact + pair * m.stride;
     unsigned nl, ne;
     float med;
-    if (n & 1u) {
-        med = key2f(radix_select<REP>(cx, cn, n / 2, hist, sh, nl, ne, nullptr, nullptr, nullptr, 1, ss.bin << 21, ss.below));
-    } else {
-        const unsigned ka = radix_select<REP>(cx, cn, n / 2 - 1, hist, sh, nl, ne, nullptr, nullptr, nullptr, 1, ss.bin << 21, ss.below);
-        float a = key2f(ka), b = a;
-        if (nl + ne <= n / 2) {  // upper middle value = next larger element: in the gathered bin, else (rare) anywhere above it
-            unsigned kb = next_larger_key(cx, cn, ka, hist);
-            if (kb == 0xffffffffu) {   // (rare) the upper middle value lies above the gathered bin: that needs the whole map
-                if (p.partial_map) {   // hand the pair to the full-map route (uniform: every lane holds the same kb)
-                    if (threadIdx.x == 0) sel[pair].ok = 0u;
-                    return;
-                }
-                kb = next_larger_key(msrc, n, ka, hist);
-            }
-            b = key2f(kb);
-        }
-        med = __fmul_rn(__fadd_rn(a, b), 0.5f);
+    const unsigned ka = radix_select<FIN_REP>(cx, ss.count, lower_middle(m.n), hist, sh, nl, ne, nullptr, nullptr, nullptr, 1,
+                                              ss.bin << 21, ss.below);
+    // (rare) the upper middle value lies above the gathered bin and only the rows around the peak exist of the map
+    // (p.partial_map): the pair is handed to the full-map route
+    if (!median_from_select(ka, m.n, nl, ne, cx, ss.count, p.partial_map ? nullptr : m.msrc, hist, med)) {
+        if (threadIdx.x == 0) sel[pair].ok = 0u;
+        return;
     }
     if (threadIdx.x != 0) return;
-    track_finish(p, pair, mag, mny, mnx, oy, ox, bv, bi, med);
+    track_finish(p, pair, m, bv, bi, med);
 }
 
-static int launch_track_fin2(const FinArgs& fa, SelState* sel, unsigned pred, int pairs, hipStream_t st) {
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_track_fin2), FIN_LDS);
-        if (rc_lds) return rc_lds;
-    }
-    const size_t n = (size_t)fa.ny * fa.nx;
-    hipLaunchKernelGGL(k_track_select, dim3((pairs + 63) / 64), dim3(64), 0, st, n, sel, pred, pairs);
-    hipLaunchKernelGGL(k_track_fin2, dim3(pairs), dim3(1024), FIN_LDS, st, fa, sel);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-// template matching: the verdicts come from k_ncc_check
-static int launch_track_fin2_checked(const FinArgs& fa, SelState* sel, int pairs, hipStream_t st) {
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_track_fin2), FIN_LDS);
-        if (rc_lds) return rc_lds;
-    }
-    hipLaunchKernelGGL(k_track_fin2, dim3(pairs), dim3(1024), FIN_LDS, st, fa, sel);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+// verdicts (preds null: n = ny * nx elements and the bin `pred` for every pair; else per pair from fa.geom and preds), then the
+// pairs whose expectation holds
+static int launch_track_fin2(const FinArgs& fa, SelState* sel, unsigned pred, const unsigned* preds, int pairs, hipStream_t st) {
+    if (const int rc = launch(k_track_select, dim3((pairs + 63) / 64), dim3(64), 0, st, sel, pairs, (unsigned)fa.ny * fa.nx, pred,
+                              fa.geom, preds))
+        return rc;
+    return launch(k_track_fin2, dim3(pairs), dim3(1024), FIN_LDS, st, fa, sel);
 }
 // the pairs whose expectation failed (all of them when it is switched off): whole selection on the (full) map
 static int launch_track_fin_rest(const FinArgs& fa, SelState* sel, int pairs, hipStream_t st) {
     FinArgs fb = fa;
     fb.skip = &sel[0].ok;
     fb.skip_stride = SEL_WORDS;
-    return launch_track_fin(fb, pairs, st);
+    return launch(k_track_fin, dim3(pairs), dim3(1024), FIN_LDS, st, fb);
 }
 
 // ------------------------------------------------------------------------------------ NCC template matching
@@ -661,7 +641,7 @@ __device__ __forceinline__ float ncc_value(const NccPair& q, int ny, int nx, int
 }
 
 // The bin of the median of |map|, guessed from NCC_SAMPLES evenly spaced elements.  grid (pairs), block 256.  Exactness never
-// depends on the guess: k_ncc_map counts what lies below / inside the bin, k_ncc_check accepts the pair only if the middle rank
+// depends on the guess: k_ncc_map counts what lies below / inside the bin, k_track_select accepts the pair only if the middle rank
 // falls inside it, every other pair takes the whole select on its map (k_track_fin).
 constexpr int NCC_SAMPLES = 4096;
 __global__ void __launch_bounds__(256) k_ncc_sample(NccArgs p, unsigned* __restrict__ pred) {
@@ -710,19 +690,6 @@ __global__ void __launch_bounds__(256) k_ncc_sample(NccArgs p, unsigned* __restr
             }
     }
 }
-
-// grid (ceil(pairs / 64)), block 64: the guess holds for pair i when the middle rank falls inside its bin and the whole bin was gathered
-__global__ void __launch_bounds__(64) k_ncc_check(const int* __restrict__ geom, const unsigned* __restrict__ pred, SelState* __restrict__ sel,
-                                                  int pairs) {
-    const int pair = blockIdx.x * 64 + threadIdx.x;
-    if (pair >= pairs) return;
-    SelState* st = sel + pair;
-    const unsigned n = (unsigned)geom[4 * pair] * (unsigned)geom[4 * pair + 1];
-    const unsigned k = (n & 1u) ? n / 2 : n / 2 - 1;
-    st->bin = pred[pair];
-    st->ok = (pred[pair] != 0u && k >= st->below && k < st->below + st->count && st->fill == st->count) ? 1u : 0u;
-}
-
 
 // zero-mean normalised cross-correlation at every "valid" window position (signal/tracking.py:157-167: the arithmetic
 // of cv2.TM_CCOEFF_NORMED / skimage.match_template).  grid (nblk, pairs), block 256; a workgroup owns at most NCC_STAGE consecutive
@@ -773,6 +740,7 @@ __global__ void __launch_bounds__(256) k_ncc_map(NccArgs p) {
             }
         }
     }
+    // (not block_argmax: the wave reduction carries `below` along and only lane 0 merges the waves)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_down(bv, o, 64);
@@ -853,19 +821,8 @@ __global__ void __launch_bounds__(256) k_gen_mag(const float2* __restrict__ R, i
         mag[fo + e] = v;
         argmax_merge(bv, bi, v, e);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_down(bv, o, 64);
-        const int oi = __shfl_down(bi, o, 64);
-        argmax_merge(bv, bi, ov, oi);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sv[threadIdx.x >> 6] = bv;
-        si[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
+    block_argmax(bv, bi, sv, si, 4);
     if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) argmax_merge(bv, bi, sv[k], si[k]);
         part_val[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = bv;
         part_idx[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = bi;
     }
@@ -909,20 +866,9 @@ using namespace b4d;
 template <int NY, bool WHITEN>
 static int launch_prod(const ProdArgs& a, int nt, int pairs, hipStream_t st) {
     using Cfg = ColCfg<NY>;
-    if (a.srcs_b) {   // tracking (phase correlation and NCC): template column transforms fused in (TPL)
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col_prod<NY, WHITEN, true>), Cfg::LDS_BYTES);
-        if (rc_lds) return rc_lds;
-        hipLaunchKernelGGL((k_col_prod<NY, WHITEN, true>), dim3(nt, pairs), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, a);
-        B4D_HIP(hipGetLastError());
-        return B4D_OK;
-    }
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col_prod<NY, WHITEN>), Cfg::LDS_BYTES);
-        if (rc_lds) return rc_lds;
-    }
-    hipLaunchKernelGGL((k_col_prod<NY, WHITEN>), dim3(nt, pairs), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, a);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    // tracking (phase correlation and NCC: srcs_b is set): template column transforms fused in (TPL)
+    void (*const kernel)(ProdArgs) = a.srcs_b ? &k_col_prod<NY, WHITEN, true> : &k_col_prod<NY, WHITEN, false>;
+    return launch(kernel, dim3(nt, pairs), dim3(Cfg::THREADS), Cfg::LDS_BYTES, st, a);
 }
 template <bool WHITEN>
 static int dispatch_prod(const b4d_plan* pl, ProdArgs a, int pairs, hipStream_t st) {
@@ -960,22 +906,47 @@ static int forward_spectra(const b4d_plan* pl, const float* frames, const RowSrc
     return dispatch_nyq<NYQ_FORWARD>(pl, na, items, st);
 }
 
+// spectra of the sources of a tracking call, once per distinct image / template (item i of spec / nyq_rows / nyq belongs to
+// srcs[i]: images, then templates): images with their columns, templates without.  Groups never straddle the two frame arrays.
+static int forward_spectra_sources(const b4d_plan* pl, const float* images, int nimg, const float* tpl_src, int ntpl,
+                                   const RowSrc* srcs, float2* spec, float* nyq_rows, float2* nyq, hipStream_t st) {
+    const size_t ny = pl->ny, half = ny * pl->nx / 2;
+    const int fc = std::max(1, pl->chunk * 2), nsrc = nimg + ntpl;
+    for (int s0 = 0; s0 < nsrc;) {
+        const bool img = s0 < nimg;
+        const int n = std::min(fc, (img ? nimg : nsrc) - s0);
+        if (const int rc = forward_spectra(pl, img ? images : tpl_src, srcs + s0, n, spec + half * s0, nyq_rows + ny * s0, nyq + ny * s0,
+                                           st, /*columns=*/img))
+            return rc;
+        s0 += n;
+    }
+    return B4D_OK;
+}
+
 namespace {
-// byte-carving helper over one hipMalloc'ed arena
+// Byte-carving helper over one hipMalloc'ed arena: every buffer starts on a 256-byte boundary.  base == nullptr is the measuring
+// pass: take() only advances `off` and returns null.
 struct Arena {
     char* base = nullptr;
     size_t off = 0, cap = 0;
     template <typename T>
     T* take(size_t n) {
         off = (off + 255) & ~(size_t)255;
-        T* p = reinterpret_cast<T*>(base + off);
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
         off += n * sizeof(T);
         return p;
     }
 };
 }  // namespace
 
-static int track_arena(b4d_plan* pl, size_t bytes, Arena* a) {
+// The plan's tracking workspace, carved by `layout(Arena&)`: the ONE statement of an entry point's buffers, which assigns every
+// pointer with take<T>(n).  It runs twice -- on a null arena to measure, then on pl->track_ws (grown when too small) -- and the
+// second pass has to end where the first one did, inside the allocation.
+template <class Layout>
+static int track_workspace(b4d_plan* pl, Layout&& layout) {
+    Arena measure;
+    layout(measure);
+    const size_t bytes = measure.off;
     if (bytes > pl->track_bytes) {
         if (pl->track_ws) (void)hipFree(pl->track_ws);
         pl->track_ws = nullptr;
@@ -984,10 +955,95 @@ static int track_arena(b4d_plan* pl, size_t bytes, Arena* a) {
         if (e != hipSuccess) return fail(B4D_ENOMEM, std::string("tracking workspace: ") + hipGetErrorString(e));
         pl->track_bytes = bytes;
     }
-    a->base = static_cast<char*>(pl->track_ws);
-    a->off = 0;
-    a->cap = pl->track_bytes;
+    Arena ar;
+    ar.base = static_cast<char*>(pl->track_ws);
+    ar.cap = pl->track_bytes;
+    layout(ar);
+    if (ar.off != bytes || ar.off > ar.cap)
+        return fail(B4D_ENOMEM, "internal error: tracking workspace carved to " + std::to_string(ar.off) + " bytes, measured " +
+                                    std::to_string(bytes) + ", allocated " + std::to_string(ar.cap));
     return B4D_OK;
+}
+
+// the sources, pairs and outputs of a tracking call, as the C ABI receives them
+struct TrackCall {
+    const float* images;
+    int nimg;
+    const float* tpl_src;
+    int ntplsrc;
+    const int32_t *tpl_frame, *tpl_roi;
+    int ntpl;
+    const int32_t *pair_img, *pair_tpl;
+    int npairs, subpixel;
+    double eps;
+    double* out;
+    int32_t* peak_ij;
+};
+
+// The source setup of every tracking route.  Validates the templates (frame index, ROI inside the lim_h x lim_w image extent)
+// and the pairs; uploads the descriptors (srcs[0 .. nimg): the images over (lim_h, lim_w), srcs[nimg ..): the template ROIs,
+// z-scored, zero elsewhere) and, in one copy, the pair index columns of npairs ints each -- image, [template, when cols == 3,]
+// nimg + template (the template's item among the sources) -- followed by `tail`; waits for the copies (the host vectors live
+// here); runs the z-score statistics of the templates and, when zscore_images, of the images.
+static int track_sources(const TrackCall& c, int ny, int nx, int lim_h, int lim_w, bool zscore_images, int cols, RowSrc* srcs,
+                         double* roi_part, int* pidx, hipStream_t st, const std::vector<int>& tail = {}) {
+    const int nimg = c.nimg, ntpl = c.ntpl, npairs = c.npairs, nsrc = nimg + ntpl;
+    for (int k = 0; k < ntpl; ++k) {
+        const int32_t* r = c.tpl_roi + 4 * k;
+        if (c.tpl_frame[k] < 0 || c.tpl_frame[k] >= c.ntplsrc || r[0] < 0 || r[1] > lim_h || r[0] >= r[1] || r[2] < 0 || r[3] > lim_w ||
+            r[2] >= r[3])
+            return fail(B4D_EINVAL, "template " + std::to_string(k) + ": frame or ROI out of range");
+    }
+    for (int i = 0; i < npairs; ++i)
+        if (c.pair_img[i] < 0 || c.pair_img[i] >= nimg || c.pair_tpl[i] < 0 || c.pair_tpl[i] >= ntpl)
+            return fail(B4D_EINVAL, "pair " + std::to_string(i) + ": index out of range");
+    std::vector<RowSrc> h(nsrc);
+    for (int i = 0; i < nimg; ++i) h[i] = RowSrc{i, 0, lim_h, 0, lim_w, 0.f, 1.f, 0};
+    for (int k = 0; k < ntpl; ++k)
+        h[nimg + k] = RowSrc{c.tpl_frame[k], c.tpl_roi[4 * k], c.tpl_roi[4 * k + 1], c.tpl_roi[4 * k + 2], c.tpl_roi[4 * k + 3], 0.f, 1.f, 0};
+    std::vector<int> hp((size_t)cols * npairs);
+    for (int i = 0; i < npairs; ++i) {
+        hp[i] = c.pair_img[i];
+        if (cols == 3) hp[(size_t)npairs + i] = c.pair_tpl[i];
+        hp[(size_t)(cols - 1) * npairs + i] = nimg + c.pair_tpl[i];
+    }
+    hp.insert(hp.end(), tail.begin(), tail.end());
+    B4D_HIP(hipMemcpyAsync(srcs, h.data(), sizeof(RowSrc) * nsrc, hipMemcpyHostToDevice, st));
+    B4D_HIP(hipMemcpyAsync(pidx, hp.data(), sizeof(int) * hp.size(), hipMemcpyHostToDevice, st));
+    B4D_HIP(hipStreamSynchronize(st));
+    if (zscore_images)
+        if (const int rc = roi_stats(c.images, ny, nx, c.eps, srcs, nimg, roi_part, st)) return rc;
+    return roi_stats(c.tpl_src, ny, nx, c.eps, srcs + nimg, ntpl, roi_part + (size_t)2 * ROI_SPLIT * nimg, st);
+}
+
+// the epilogue arguments every route sets alike, for the launch group that starts at pair p0
+static FinArgs fin_args(const TrackCall& c, int p0, const float* mag, const float* part_val, const int* part_idx, int nblk, int ny,
+                        int nx) {
+    FinArgs fa{};
+    fa.mag = mag;
+    fa.part_val = part_val;
+    fa.part_idx = part_idx;
+    fa.out = c.out + (size_t)p0 * 4;
+    fa.peak_ij = c.peak_ij ? c.peak_ij + (size_t)p0 * 2 : nullptr;
+    fa.ny = ny;
+    fa.nx = nx;
+    fa.nblk = nblk;
+    fa.subpixel = c.subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
+    fa.eps = c.eps;
+    return fa;
+}
+
+// the arguments of an inverse row pass that every caller sets alike
+static RowOutArgs row_out_args(const b4d_plan* pl, const float2* g, const float* gnyq, float* out) {
+    RowOutArgs ra{};
+    ra.g = g;
+    ra.gnyq = gnyq;
+    ra.out = out;
+    ra.tw = pl->tw_x;
+    ra.scale = 1.0f / ((float)pl->nx * (float)pl->ny);
+    ra.ny = pl->ny;
+    ra.ct_w = pl->ct_w;
+    return ra;
 }
 
 // Fi * conj(Ft) [whitened] -> inverse column pass (tiles + Nyquist column) for `pairs` pairs
@@ -1019,170 +1075,102 @@ static int product_inverse(const b4d_plan* pl, const float2* spec, const float2*
 }
 
 int normalise_by_absmax(float* x, size_t n, int batch, float* scratch, hipStream_t st) {
-    hipLaunchKernelGGL(k_absmax_part, dim3(256, batch), dim3(1024), 0, st, x, n, scratch);
-    hipLaunchKernelGGL(k_scale_by_max, dim3(1024, batch), dim3(256), 0, st, x, n, scratch, 256);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    if (const int rc = launch(k_absmax_part, dim3(256, batch), dim3(1024), 0, st, x, n, scratch)) return rc;
+    return launch(k_scale_by_max, dim3(1024, batch), dim3(256), 0, st, x, n, scratch, 256);
 }
 
-// phase correlation on a general-length plan (DFT-matrix or fused mixed-radix transforms): same steps as the
-// power-of-two path with full complex spectra
 // General sizes whose two sides have mixed-radix kernels (b4d_wiener_mr.hip; 2560 x 2160 detector frames ...): half spectra in
 // the transposed [k][ky] layout, three passes per pair (product + inverse columns, inverse row pairs -> |corr| map + arg-max
 // partials, selection) instead of full-complex DFT-matrix / fused transforms with transposes in between.
-static int wmr_phase_correlation(b4d_plan* pl, const float* images, int nimg, const float* tpl_src, const int32_t* tpl_frame,
-                                 const int32_t* tpl_roi, int ntpl, const int32_t* pair_img, const int32_t* pair_tpl, int npairs,
-                                 int subpixel, double eps, double* out, int32_t* peak_ij, hipStream_t st) {
-    const int ny = pl->ny, nx = pl->nx, nsrc = nimg + ntpl, hp = (ny + 1) / 2, qpf = wmr_quads_per_frame(ny);
+static int wmr_phase_correlation(b4d_plan* pl, const TrackCall& c, hipStream_t st) {
+    const int ny = pl->ny, nx = pl->nx, nimg = c.nimg, nsrc = nimg + c.ntpl, npairs = c.npairs, hp = (ny + 1) / 2;
+    const int qpf = wmr_quads_per_frame(ny);
     const int predict_mode = g_opt_track_predict.load();   // one route per call
     const size_t npix = (size_t)ny * nx, selems = wmr_spectrum_elems(ny, nx);
     const int sc = std::max(1, pl->chunk), pc = std::max(1, std::min(npairs, pl->chunk));
-    size_t need = 0;
-    auto add = [&](size_t b) { need += ((b + 255) & ~(size_t)255) + 256; };
-    add(sizeof(float2) * selems * nsrc);
-    add(sizeof(float) * npix * sc);
-    add(sizeof(float) * (size_t)hp * sc);
-    add(sizeof(RowSrc) * nsrc);
-    add(sizeof(double) * 2 * ROI_SPLIT * nsrc);
-    add(sizeof(int) * 2 * (size_t)npairs);
-    add(sizeof(float2) * selems * pc);
-    add(sizeof(float) * npix * pc);
-    add(sizeof(float) * npix * pc);
-    add(sizeof(float) * (size_t)qpf * pc);
-    add(sizeof(int) * (size_t)qpf * pc);
-    add(sizeof(unsigned) * SEL_WORDS * (size_t)pc);
-    Arena ar;
-    int rc = track_arena(pl, need, &ar);
+    float2 *spec, *G;
+    float *canvas, *scratch, *mag, *medws, *pval;
+    RowSrc* srcs;
+    double* roi_part;
+    int *pidx, *pind;
+    SelState* msel;
+    int rc = track_workspace(pl, [&](Arena& ar) {
+        spec = ar.take<float2>(selems * nsrc);
+        canvas = ar.take<float>(npix * sc);
+        scratch = ar.take<float>((size_t)hp * sc);
+        srcs = ar.take<RowSrc>(nsrc);
+        roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
+        pidx = ar.take<int>(2 * (size_t)npairs);
+        G = ar.take<float2>(selems * pc);
+        mag = ar.take<float>(npix * pc);
+        medws = ar.take<float>(npix * pc);
+        pval = ar.take<float>((size_t)qpf * pc);
+        pind = ar.take<int>((size_t)qpf * pc);
+        msel = ar.take<SelState>(pc);
+    });
     if (rc) return rc;
-    float2* spec = ar.take<float2>(selems * nsrc);
-    float* canvas = ar.take<float>(npix * sc);
-    float* scratch = ar.take<float>((size_t)hp * sc);
-    RowSrc* srcs = ar.take<RowSrc>(nsrc);
-    double* roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
-    int* pidx = ar.take<int>(2 * (size_t)npairs);
-    float2* G = ar.take<float2>(selems * pc);
-    float* mag = ar.take<float>(npix * pc);
-    float* medws = ar.take<float>(npix * pc);
-    float* pval = ar.take<float>((size_t)qpf * pc);
-    int* pind = ar.take<int>((size_t)qpf * pc);
-    SelState* msel = reinterpret_cast<SelState*>(ar.take<unsigned>((size_t)SEL_WORDS * pc));
-    std::vector<RowSrc> h(nsrc);
-    for (int i = 0; i < nimg; ++i) h[i] = RowSrc{i, 0, ny, 0, nx, 0.f, 1.f, 0};
-    for (int k = 0; k < ntpl; ++k)
-        h[nimg + k] = RowSrc{tpl_frame[k], tpl_roi[4 * k], tpl_roi[4 * k + 1], tpl_roi[4 * k + 2], tpl_roi[4 * k + 3], 0.f, 1.f, 0};
-    std::vector<int> hpi(2 * (size_t)npairs);
-    for (int i = 0; i < npairs; ++i) {
-        hpi[i] = pair_img[i];
-        hpi[npairs + i] = nimg + pair_tpl[i];
-    }
-    B4D_HIP(hipMemcpyAsync(srcs, h.data(), sizeof(RowSrc) * nsrc, hipMemcpyHostToDevice, st));
-    B4D_HIP(hipMemcpyAsync(pidx, hpi.data(), sizeof(int) * hpi.size(), hipMemcpyHostToDevice, st));
-    B4D_HIP(hipStreamSynchronize(st));
-    if ((rc = roi_stats(images, ny, nx, eps, srcs, nimg, roi_part, st))) return rc;
-    if ((rc = roi_stats(tpl_src, ny, nx, eps, srcs + nimg, ntpl, roi_part + (size_t)2 * ROI_SPLIT * nimg, st))) return rc;
+    if ((rc = track_sources(c, ny, nx, ny, nx, true, 2, srcs, roi_part, pidx, st))) return rc;
     const dim3 eg((unsigned)((npix + 255) / 256));
     for (int s0 = 0; s0 < nsrc;) {   // spectra, once per distinct image / template; never straddle the two frame arrays
         const int n = std::min(sc, (s0 < nimg ? nimg : nsrc) - s0);
-        hipLaunchKernelGGL(k_embed_roi, dim3(eg.x, n), dim3(256), 0, st, s0 < nimg ? images : tpl_src, ny, nx, srcs + s0, canvas);
-        B4D_HIP(hipGetLastError());
+        if ((rc = launch(k_embed_roi, dim3(eg.x, n), dim3(256), 0, st, s0 < nimg ? c.images : c.tpl_src, ny, nx, srcs + s0, canvas))) return rc;
         if ((rc = wmr_forward_spectra(canvas, n, ny, nx, pl->tw_x, pl->tw_y, spec + selems * s0, scratch, st))) return rc;
         s0 += n;
     }
     for (int p0 = 0; p0 < npairs; p0 += pc) {
         const int np = std::min(pc, npairs - p0);
-        if ((rc = wmr_product_inverse(spec, spec, pidx + p0, pidx + npairs + p0, np, ny, nx, pl->tw_y, G, 1, (float)eps, B4D_REMOVE_MEAN, st))) return rc;
+        if ((rc = wmr_product_inverse(spec, spec, pidx + p0, pidx + npairs + p0, np, ny, nx, pl->tw_y, G, 1, (float)c.eps, B4D_REMOVE_MEAN, st))) return rc;
         const unsigned pred = predicted_median_bin(npix, predict_mode);
         B4D_HIP(hipMemsetAsync(msel, 0, sizeof(SelState) * (size_t)pc, st));
         if ((rc = wmr_rows_magnitude(G, np, ny, nx, pl->tw_x, mag, pval, pind, reinterpret_cast<unsigned*>(msel), SEL_WORDS, pred, medws, st)))
             return rc;
-        FinArgs fa{};
-        fa.mag = mag;
+        FinArgs fa = fin_args(c, p0, mag, pval, pind, qpf, ny, nx);
         fa.compact = medws;
-        fa.part_val = pval;
-        fa.part_idx = pind;
-        fa.out = out + (size_t)p0 * 4;
-        fa.peak_ij = peak_ij ? peak_ij + (size_t)p0 * 2 : nullptr;
-        fa.ny = ny;
-        fa.nx = nx;
-        fa.nblk = qpf;
-        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
-        fa.eps = eps;
-        if ((rc = launch_track_fin2(fa, msel, pred, np, st))) return rc;
+        if ((rc = launch_track_fin2(fa, msel, pred, nullptr, np, st))) return rc;
         if ((rc = launch_track_fin_rest(fa, msel, np, st))) return rc;
     }
     return B4D_OK;
 }
 
-static int general_phase_correlation(b4d_plan* pl, const float* images, int nimg, const float* tpl_src, const int32_t* tpl_frame,
-                                     const int32_t* tpl_roi, int ntpl, const int32_t* pair_img, const int32_t* pair_tpl, int npairs,
-                                     int subpixel, double eps, double* out, int32_t* peak_ij, hipStream_t st) {
-    if (pl->wmr)
-        return wmr_phase_correlation(pl, images, nimg, tpl_src, tpl_frame, tpl_roi, ntpl, pair_img, pair_tpl, npairs, subpixel, eps, out,
-                                     peak_ij, st);
-    const int ny = pl->ny, nx = pl->nx, npix = ny * nx, nsrc = nimg + ntpl, nblk = 256;
+// phase correlation on a general-length plan: the mixed-radix route above where both sides have kernels, else the same steps
+// as the power-of-two path with full complex spectra (DFT-matrix or fused transforms) and the whole select on every map
+static int general_phase_correlation(b4d_plan* pl, const TrackCall& c, hipStream_t st) {
+    if (pl->wmr) return wmr_phase_correlation(pl, c, st);
+    const int ny = pl->ny, nx = pl->nx, npix = ny * nx, nimg = c.nimg, nsrc = nimg + c.ntpl, npairs = c.npairs, nblk = 256;
     const int pc = std::max(1, std::min(npairs, pl->chunk));
-    size_t need = 0;
-    auto add = [&](size_t b) { need += ((b + 255) & ~(size_t)255) + 256; };
-    add(sizeof(float2) * (size_t)npix * nsrc);
-    add(sizeof(float) * (size_t)npix * pl->chunk);
-    add(sizeof(RowSrc) * nsrc);
-    add(sizeof(double) * 2 * ROI_SPLIT * nsrc);
-    add(sizeof(int) * 2 * (size_t)npairs);
-    add(sizeof(float) * (size_t)npix * pc);
-    add(sizeof(float) * (size_t)nblk * pc);
-    add(sizeof(int) * (size_t)nblk * pc);
-    Arena ar;
-    int rc = track_arena(pl, need, &ar);
+    float2* spec;
+    float *canvas, *mag, *pval;
+    RowSrc* srcs;
+    double* roi_part;
+    int *pidx, *pind;
+    int rc = track_workspace(pl, [&](Arena& ar) {
+        spec = ar.take<float2>((size_t)npix * nsrc);
+        canvas = ar.take<float>((size_t)npix * pl->chunk);
+        srcs = ar.take<RowSrc>(nsrc);
+        roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
+        pidx = ar.take<int>(2 * (size_t)npairs);
+        mag = ar.take<float>((size_t)npix * pc);
+        pval = ar.take<float>((size_t)nblk * pc);
+        pind = ar.take<int>((size_t)nblk * pc);
+    });
     if (rc) return rc;
-    float2* spec = ar.take<float2>((size_t)npix * nsrc);
-    float* canvas = ar.take<float>((size_t)npix * pl->chunk);
-    RowSrc* srcs = ar.take<RowSrc>(nsrc);
-    double* roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
-    int* pidx = ar.take<int>(2 * (size_t)npairs);
-    float* mag = ar.take<float>((size_t)npix * pc);
-    float* pval = ar.take<float>((size_t)nblk * pc);
-    int* pind = ar.take<int>((size_t)nblk * pc);
-    std::vector<RowSrc> h(nsrc);
-    for (int i = 0; i < nimg; ++i) h[i] = RowSrc{i, 0, ny, 0, nx, 0.f, 1.f, 0};
-    for (int k = 0; k < ntpl; ++k)
-        h[nimg + k] = RowSrc{tpl_frame[k], tpl_roi[4 * k], tpl_roi[4 * k + 1], tpl_roi[4 * k + 2], tpl_roi[4 * k + 3], 0.f, 1.f, 0};
-    std::vector<int> hp(2 * (size_t)npairs);
-    for (int i = 0; i < npairs; ++i) {
-        hp[i] = pair_img[i];
-        hp[npairs + i] = nimg + pair_tpl[i];
-    }
-    B4D_HIP(hipMemcpyAsync(srcs, h.data(), sizeof(RowSrc) * nsrc, hipMemcpyHostToDevice, st));
-    B4D_HIP(hipMemcpyAsync(pidx, hp.data(), sizeof(int) * hp.size(), hipMemcpyHostToDevice, st));
-    B4D_HIP(hipStreamSynchronize(st));
-    if ((rc = roi_stats(images, ny, nx, eps, srcs, nimg, roi_part, st))) return rc;
-    if ((rc = roi_stats(tpl_src, ny, nx, eps, srcs + nimg, ntpl, roi_part + (size_t)2 * ROI_SPLIT * nimg, st))) return rc;
+    if ((rc = track_sources(c, ny, nx, ny, nx, true, 2, srcs, roi_part, pidx, st))) return rc;
     const dim3 eg((npix + 255) / 256);
     for (int s0 = 0; s0 < nsrc;) {   // spectra, once per distinct image / template; never straddle the two frame arrays
         const int n = std::min(pl->chunk, (s0 < nimg ? nimg : nsrc) - s0);
-        hipLaunchKernelGGL(k_embed_roi, dim3(eg.x, n), dim3(256), 0, st, s0 < nimg ? images : tpl_src, ny, nx, srcs + s0, canvas);
-        B4D_HIP(hipGetLastError());
+        if ((rc = launch(k_embed_roi, dim3(eg.x, n), dim3(256), 0, st, s0 < nimg ? c.images : c.tpl_src, ny, nx, srcs + s0, canvas))) return rc;
         if ((rc = general_dft2(pl, canvas, true, n, 0, pl->gbuf1, spec + (size_t)s0 * npix, st))) return rc;
         s0 += n;
     }
     for (int p0 = 0; p0 < npairs; p0 += pc) {
         const int np = std::min(pc, npairs - p0);
-        hipLaunchKernelGGL(k_gen_cps, dim3(eg.x, np), dim3(256), 0, st, spec, pidx + p0, pidx + npairs + p0, npix, (float)eps, pl->gbuf2);
-        B4D_HIP(hipGetLastError());
+        if ((rc = launch(k_gen_cps, dim3(eg.x, np), dim3(256), 0, st, spec, pidx + p0, pidx + npairs + p0, npix, (float)c.eps, pl->gbuf2)))
+            return rc;
         if ((rc = general_dft2(pl, pl->gbuf2, false, np, 1, pl->gbuf1, pl->gbuf3, st))) return rc;
-        hipLaunchKernelGGL(k_gen_mag, dim3(nblk, np), dim3(256), 0, st, pl->gbuf3, ny, nx, 1.0f / ((float)nx * (float)ny), mag, pval, pind);
-        FinArgs fa{};
-        fa.mag = mag;
-        fa.part_val = pval;
-        fa.part_idx = pind;
-        fa.out = out + (size_t)p0 * 4;
-        fa.peak_ij = peak_ij ? peak_ij + (size_t)p0 * 2 : nullptr;
-        fa.ny = ny;
-        fa.nx = nx;
-        fa.nblk = nblk;
-        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
-        fa.eps = eps;
-        if ((rc = launch_track_fin(fa, np, st))) return rc;
-        B4D_HIP(hipGetLastError());
+        if ((rc = launch(k_gen_mag, dim3(nblk, np), dim3(256), 0, st, pl->gbuf3, ny, nx, 1.0f / ((float)nx * (float)ny), mag, pval, pind)))
+            return rc;
+        const FinArgs fa = fin_args(c, p0, mag, pval, pind, nblk, ny, nx);
+        if ((rc = launch(k_track_fin, dim3(np), dim3(1024), FIN_LDS, st, fa))) return rc;
     }
     return B4D_OK;
 }
@@ -1197,24 +1185,20 @@ int b4d_xcorr2d(b4d_plan* pl, const float* a, const float* b, int batch, float* 
     if (pl->general) return general_xcorr(pl, a, b, batch, corr, flags, st);
     const size_t fpix = (size_t)pl->ny * pl->nx, half = fpix / 2, ny = pl->ny;
     const int chunk = pl->chunk;
-    size_t need = 0;
-    auto add = [&](size_t bytes) { need += ((bytes + 255) & ~(size_t)255) + 256; };
-    for (int i = 0; i < 3; ++i) add(sizeof(float2) * half * chunk);
-    for (int i = 0; i < 2; ++i) add(sizeof(float2) * ny * chunk);
-    for (int i = 0; i < 3; ++i) add(sizeof(float) * ny * chunk);
-    add(sizeof(float) * 256 * chunk);
-    Arena ar;
-    int rc = track_arena(pl, need, &ar);
+    float2 *sa, *sb, *g, *fa, *fb;
+    float *ra_rows, *rb_rows, *gnyq, *part0;
+    int rc = track_workspace(pl, [&](Arena& ar) {
+        sa = ar.take<float2>(half * chunk);
+        sb = ar.take<float2>(half * chunk);
+        g = ar.take<float2>(half * chunk);
+        fa = ar.take<float2>(ny * chunk);
+        fb = ar.take<float2>(ny * chunk);
+        ra_rows = ar.take<float>(ny * chunk);
+        rb_rows = ar.take<float>(ny * chunk);
+        gnyq = ar.take<float>(ny * chunk);
+        part0 = ar.take<float>((size_t)256 * chunk);
+    });
     if (rc) return rc;
-    float2* sa = ar.take<float2>(half * chunk);
-    float2* sb = ar.take<float2>(half * chunk);
-    float2* g = ar.take<float2>(half * chunk);
-    float2* fa = ar.take<float2>(ny * chunk);
-    float2* fb = ar.take<float2>(ny * chunk);
-    float* ra_rows = ar.take<float>(ny * chunk);
-    float* rb_rows = ar.take<float>(ny * chunk);
-    float* gnyq = ar.take<float>(ny * chunk);
-    float* part0 = ar.take<float>((size_t)256 * chunk);
     // two-lane launch groups (Lanes, b4d_fft2d.hpp): 2048^2 16.3 -> 17.1 k pairs/s, 1024^2 50.5 -> 54.7 k (tools/dev_xcorr_chunk.py);
     // lane l works in slot l (sub items) of every chunk buffer
     // (groups of half the plan's chunk: the column kernels of this route want thousands of tiles per launch, 4-frame groups lose)
@@ -1232,16 +1216,7 @@ int b4d_xcorr2d(b4d_plan* pl, const float* a, const float* b, int batch, float* 
         if ((rc = forward_spectra(pl, a + b0 * fpix, nullptr, nb, sa_, ra_, fa_, ls))) break;
         if ((rc = forward_spectra(pl, b + b0 * fpix, nullptr, nb, sb_, rb_, fb_, ls))) break;
         if ((rc = product_inverse<false>(pl, sa_, fa_, nullptr, nullptr, sb_, fb_, nb, g_, gn_, 0.f, flags, ls))) break;
-        RowOutArgs ra{};
-        ra.g = g_;
-        ra.gnyq = gn_;
-        ra.out = corr + b0 * fpix;
-        ra.tw = pl->tw_x;
-        ra.scale = 1.0f / ((float)pl->nx * (float)pl->ny);
-        ra.ny = pl->ny;
-        ra.ct_w = pl->ct_w;
-        ra.flags = 0;
-        if ((rc = dispatch_c2r(pl, ra, nb, ls, C2R_OUT))) break;
+        if ((rc = dispatch_c2r(pl, row_out_args(pl, g_, gn_, corr + b0 * fpix), nb, ls, C2R_OUT))) break;
         if (flags & B4D_NORM_PEAK)
             if ((rc = normalise_by_absmax(corr + b0 * fpix, fpix, nb, part, ls))) break;
     }
@@ -1257,21 +1232,11 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
         return fail(B4D_EINVAL, "null argument");
     if (nimg < 1 || ntplsrc < 1 || ntpl < 1 || npairs < 1) return fail(B4D_EINVAL, "counts must be >= 1");
     B4D_PLAN_LOCK(pl);
+    const TrackCall c{images, nimg, tpl_src, ntplsrc, tpl_frame, tpl_roi, ntpl, pair_img, pair_tpl, npairs, subpixel, eps, out, peak_ij};
+    hipStream_t st = (hipStream_t)stream;
+    if (pl->general) return general_phase_correlation(pl, c, st);
     const int ny = pl->ny, nx = pl->nx;
     const int predict_mode = g_opt_track_predict.load();   // one route per call
-    for (int k = 0; k < ntpl; ++k) {
-        const int32_t* r = tpl_roi + 4 * k;
-        if (tpl_frame[k] < 0 || tpl_frame[k] >= ntplsrc || r[0] < 0 || r[1] > ny || r[0] >= r[1] || r[2] < 0 || r[3] > nx ||
-            r[2] >= r[3])
-            return fail(B4D_EINVAL, "template " + std::to_string(k) + ": frame or ROI out of range");
-    }
-    for (int i = 0; i < npairs; ++i)
-        if (pair_img[i] < 0 || pair_img[i] >= nimg || pair_tpl[i] < 0 || pair_tpl[i] >= ntpl)
-            return fail(B4D_EINVAL, "pair " + std::to_string(i) + ": index out of range");
-    hipStream_t st = (hipStream_t)stream;
-    if (pl->general)
-        return general_phase_correlation(pl, images, nimg, tpl_src, tpl_frame, tpl_roi, ntpl, pair_img, pair_tpl, npairs, subpixel, eps,
-                                         out, peak_ij, st);
     const size_t fpix = (size_t)ny * nx, half = fpix / 2;
     // pairs per launch group; a call of more than one group runs on two lanes (Lanes, b4d_fft2d.hpp: alternate groups on the
     // caller's stream and the library's second one, each with its own slot of the per-group buffers)
@@ -1279,67 +1244,31 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
     const bool two = npairs > pc_one / 2 && pc_one >= 64 && g_opt_lanes.load() != 0;   // cfg3 (1152 pairs, groups of 192): 226 -> 231 k pairs/s
     const int pc = two ? (pc_one + 1) / 2 : pc_one, nslot = two ? 2 : 1;
     const int nsrc = nimg + ntpl;
-    size_t need = 0;
-    auto add = [&](size_t b) { need += ((b + 255) & ~(size_t)255) + 256; };
-    add(sizeof(float2) * half * nsrc);        // spectra
-    add(sizeof(float2) * (size_t)ny * nsrc);  // Nyquist column spectra
-    add(sizeof(float) * (size_t)ny * nsrc);   // Nyquist bins after the row pass
-    add(sizeof(RowSrc) * nsrc);
-    add(sizeof(double) * 2 * ROI_SPLIT * nsrc);
-    add(sizeof(int) * 2 * (size_t)npairs);
-    add(sizeof(float2) * half * pc * nslot);          // G
-    add(sizeof(float) * (size_t)ny * pc * nslot);     // G of the Nyquist column
-    add(sizeof(float) * fpix * pc * nslot);           // magnitude maps
-    add(sizeof(float) * fpix * pc * nslot);           // median scratch (gathered bin)
-    add(sizeof(float) * 2048 * (size_t)pc * nslot);
-    add(sizeof(int) * 2048 * (size_t)pc * nslot);
-    add(sizeof(unsigned) * SEL_WORDS * (size_t)pc * nslot);   // select state of the median
-    Arena ar;
-    int rc = track_arena(pl, need, &ar);
+    float2 *spec, *nyq, *g0;
+    float *nyq_rows, *gnyq0, *mag0, *medws0, *pval0;
+    RowSrc* srcs;
+    double* roi_part;
+    int *pidx, *pind0;
+    SelState* msel0;
+    int rc = track_workspace(pl, [&](Arena& ar) {
+        spec = ar.take<float2>(half * nsrc);
+        nyq = ar.take<float2>((size_t)ny * nsrc);        // Nyquist column spectra
+        nyq_rows = ar.take<float>((size_t)ny * nsrc);    // Nyquist bins after the row pass
+        srcs = ar.take<RowSrc>(nsrc);
+        roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
+        pidx = ar.take<int>(2 * (size_t)npairs);
+        g0 = ar.take<float2>(half * pc * nslot);
+        gnyq0 = ar.take<float>((size_t)ny * pc * nslot);   // G of the Nyquist column
+        mag0 = ar.take<float>(fpix * pc * nslot);          // magnitude maps
+        medws0 = ar.take<float>(fpix * pc * nslot);        // median scratch (gathered bin)
+        pval0 = ar.take<float>((size_t)2048 * pc * nslot);
+        pind0 = ar.take<int>((size_t)2048 * pc * nslot);
+        msel0 = ar.take<SelState>((size_t)pc * nslot);     // select state of the median
+    });
     if (rc) return rc;
-    float2* spec = ar.take<float2>(half * nsrc);
-    float2* nyq = ar.take<float2>((size_t)ny * nsrc);
-    float* nyq_rows = ar.take<float>((size_t)ny * nsrc);
-    RowSrc* srcs = ar.take<RowSrc>(nsrc);
-    double* roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
-    int* pidx = ar.take<int>(2 * (size_t)npairs);
-    float2* g0 = ar.take<float2>(half * pc * nslot);
-    float* gnyq0 = ar.take<float>((size_t)ny * pc * nslot);
-    float* mag0 = ar.take<float>(fpix * pc * nslot);
-    float* medws0 = ar.take<float>(fpix * pc * nslot);
-    float* pval0 = ar.take<float>((size_t)2048 * pc * nslot);
-    int* pind0 = ar.take<int>((size_t)2048 * pc * nslot);
-    SelState* msel0 = reinterpret_cast<SelState*>(ar.take<unsigned>((size_t)SEL_WORDS * pc * nslot));
-
-    // ---- source descriptors: images (full frame, z-scored), then templates (ROI, z-scored, zero elsewhere)
-    std::vector<RowSrc> h(nsrc);
-    for (int i = 0; i < nimg; ++i) h[i] = RowSrc{i, 0, ny, 0, nx, 0.f, 1.f, 0};
-    for (int k = 0; k < ntpl; ++k)
-        h[nimg + k] = RowSrc{tpl_frame[k], tpl_roi[4 * k], tpl_roi[4 * k + 1], tpl_roi[4 * k + 2], tpl_roi[4 * k + 3], 0.f, 1.f, 0};
-    std::vector<int> hp(2 * (size_t)npairs);
-    for (int i = 0; i < npairs; ++i) {
-        hp[i] = pair_img[i];
-        hp[npairs + i] = nimg + pair_tpl[i];
-    }
-    B4D_HIP(hipMemcpyAsync(srcs, h.data(), sizeof(RowSrc) * nsrc, hipMemcpyHostToDevice, st));
-    B4D_HIP(hipMemcpyAsync(pidx, hp.data(), sizeof(int) * hp.size(), hipMemcpyHostToDevice, st));
-    B4D_HIP(hipStreamSynchronize(st));  // h / hp are stack-owned
-    if ((rc = roi_stats(images, ny, nx, eps, srcs, nimg, roi_part, st))) return rc;
-    if ((rc = roi_stats(tpl_src, ny, nx, eps, srcs + nimg, ntpl, roi_part + (size_t)2 * ROI_SPLIT * nimg, st))) return rc;
-    // ---- spectra (once per distinct image / template)
-    const int fc = std::max(1, pl->chunk * 2);
-    for (int i0 = 0; i0 < nimg; i0 += fc) {
-        const int n = std::min(fc, nimg - i0);
-        if ((rc = forward_spectra(pl, images, srcs + i0, n, spec + half * i0, nyq_rows + (size_t)ny * i0,
-                                  nyq + (size_t)ny * i0, st)))
-            return rc;
-    }
-    for (int k0 = 0; k0 < ntpl; k0 += fc) {
-        const int n = std::min(fc, ntpl - k0), o = nimg + k0;
-        if ((rc = forward_spectra(pl, tpl_src, srcs + o, n, spec + half * o, nyq_rows + (size_t)ny * o,
-                                  nyq + (size_t)ny * o, st, /*columns=*/false)))   // transformed per pair in k_col_prod<.., TPL>
-            return rc;
-    }
+    // ---- sources: images (full frame, z-scored), then templates (ROI, z-scored, zero elsewhere), and their spectra
+    if ((rc = track_sources(c, ny, nx, ny, nx, true, 2, srcs, roi_part, pidx, st))) return rc;
+    if ((rc = forward_spectra_sources(pl, images, nimg, tpl_src, ntpl, srcs, spec, nyq_rows, nyq, st))) return rc;
     // ---- pairs
     Lanes ln;
     if ((rc = ln.fork(pl, st, two))) return rc;
@@ -1360,14 +1289,7 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
         if ((rc = product_inverse<true>(pl, spec, nyq, pidx + p0, pidx + npairs + p0, spec, nyq, np, g, gnyq, (float)eps,
                                         B4D_REMOVE_MEAN, ls, srcs)))
             return rc;
-        RowOutArgs ra{};
-        ra.g = g;
-        ra.gnyq = gnyq;
-        ra.out = mag;
-        ra.tw = pl->tw_x;
-        ra.scale = 1.0f / ((float)nx * (float)ny);
-        ra.ny = ny;
-        ra.ct_w = pl->ct_w;
+        RowOutArgs ra = row_out_args(pl, g, gnyq, mag);
         ra.part_val = pval;
         ra.part_idx = pind;
         const unsigned pred = predicted_median_bin(fpix, predict_mode);
@@ -1388,20 +1310,10 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
             rr.nblk = nblk;
             if ((rc = dispatch_c2r(pl, rr, np, ls, C2R_ROWS))) return rc;
         }
-        FinArgs fa{};
-        fa.mag = mag;
+        FinArgs fa = fin_args(c, p0, mag, pval, pind, nblk, ny, nx);
         fa.compact = medws;
-        fa.part_val = pval;
-        fa.part_idx = pind;
-        fa.out = out + (size_t)p0 * 4;
-        fa.peak_ij = peak_ij ? peak_ij + (size_t)p0 * 2 : nullptr;
-        fa.ny = ny;
-        fa.nx = nx;
-        fa.nblk = nblk;
-        fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
-        fa.eps = eps;
         fa.partial_map = nomap ? 1 : 0;
-        if ((rc = launch_track_fin2(fa, msel, pred, np, ls))) return rc;
+        if ((rc = launch_track_fin2(fa, msel, pred, nullptr, np, ls))) return rc;
         if (nomap) {   // full maps for the pairs left over (verdict word of the select state != 0: nothing to do)
             RowOutArgs rf = ra;
             rf.nomap = 0;
@@ -1411,10 +1323,8 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
             if ((rc = dispatch_c2r(pl, rf, np, ls, C2R_MAG))) return rc;
         }
         if ((rc = launch_track_fin_rest(fa, msel, np, ls))) return rc;
-        B4D_HIP(hipGetLastError());
     }
-    if ((rc = ln.close())) return rc;
-    return B4D_OK;
+    return ln.close();
 }
 
 int b4d_template_match(b4d_plan* pl, const float* images, int nimg, const float* tpl_src, int ntplsrc,
@@ -1430,28 +1340,12 @@ int b4d_template_match(b4d_plan* pl, const float* images, int nimg, const float*
     if (img_h <= 0) img_h = ny;
     if (img_w <= 0) img_w = nx;
     if (img_h > ny || img_w > nx) return fail(B4D_EINVAL, "image extent exceeds the canvas");
-    for (int k = 0; k < ntpl; ++k) {
-        const int32_t* r = tpl_roi + 4 * k;
-        if (tpl_frame[k] < 0 || tpl_frame[k] >= ntplsrc || r[0] < 0 || r[1] > img_h || r[0] >= r[1] || r[2] < 0 || r[3] > img_w ||
-            r[2] >= r[3])
-            return fail(B4D_EINVAL, "template " + std::to_string(k) + ": frame or ROI out of range");
-    }
-    for (int i = 0; i < npairs; ++i)
-        if (pair_img[i] < 0 || pair_img[i] >= nimg || pair_tpl[i] < 0 || pair_tpl[i] >= ntpl)
-            return fail(B4D_EINVAL, "pair " + std::to_string(i) + ": index out of range");
+    const TrackCall c{images, nimg, tpl_src, ntplsrc, tpl_frame, tpl_roi, ntpl, pair_img, pair_tpl, npairs, subpixel, eps, out, peak_ij};
     hipStream_t st = (hipStream_t)stream;
     const size_t fpix = (size_t)ny * nx, half = fpix / 2, satn = (size_t)(ny + 1) * (nx + 1);
     const int pc = std::max(1, std::min(npairs, pl->chunk * 2));
     // workgroups per map: at most NCC_STAGE elements each (the gathered median bin is staged in LDS)
     const int nsrc = nimg + ntpl, nblk = std::max(256, (int)(((size_t)img_h * img_w + NCC_STAGE - 1) / NCC_STAGE));
-    size_t need = 0;
-    auto add = [&](size_t b) { need += ((b + 255) & ~(size_t)255) + 256; };
-    add(sizeof(float2) * half * nsrc);
-    add(sizeof(float2) * (size_t)ny * nsrc);
-    add(sizeof(float) * (size_t)ny * nsrc);
-    add(sizeof(RowSrc) * nsrc);
-    add(sizeof(double) * 2 * ROI_SPLIT * nsrc);
-    add(sizeof(int) * 3 * (size_t)npairs);
     std::vector<int> widths, heights, widx(ntpl);   // distinct template shapes: one pair of window-sum tables per (shape, image)
     for (int k = 0; k < ntpl; ++k) {
         const int w = tpl_roi[4 * k + 3] - tpl_roi[4 * k + 2], hh = tpl_roi[4 * k + 1] - tpl_roi[4 * k];
@@ -1464,148 +1358,89 @@ int b4d_template_match(b4d_plan* pl, const float* images, int nimg, const float*
         widx[k] = (int)j;
     }
     const size_t nw = widths.size();
-    add(sizeof(double) * satn * nimg * nw);
-    add(sizeof(double) * satn * nimg * nw);
-    add(sizeof(int) * (size_t)ntpl);
-    add(sizeof(double) * 2 * (size_t)ntpl);
-    add(sizeof(float2) * half * pc);
-    add(sizeof(float) * (size_t)ny * pc);
-    for (int i = 0; i < 4; ++i) add(sizeof(float) * fpix * pc);
-    add(sizeof(float) * (size_t)nblk * pc);
-    add(sizeof(int) * (size_t)nblk * pc);
-    add(sizeof(int) * 4 * (size_t)pc);
-    add(sizeof(unsigned) * (size_t)pc);
-    add(sizeof(unsigned) * SEL_WORDS * (size_t)pc);
-    Arena ar;
-    int rc = track_arena(pl, need, &ar);
+    float2 *spec, *nyq, *g;
+    float *nyq_rows, *gnyq, *xc, *ncc, *absncc, *pval, *gathered;
+    RowSrc* srcs;
+    double *roi_part, *sat1, *sat2, *tstat;
+    int *pidx, *pind, *geom;
+    unsigned* pred;
+    SelState* msel;
+    int rc = track_workspace(pl, [&](Arena& ar) {
+        spec = ar.take<float2>(half * nsrc);
+        nyq = ar.take<float2>((size_t)ny * nsrc);
+        nyq_rows = ar.take<float>((size_t)ny * nsrc);
+        srcs = ar.take<RowSrc>(nsrc);
+        roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
+        pidx = ar.take<int>(3 * (size_t)npairs + ntpl);   // image, template, template's item among the sources; shape slots
+        sat1 = ar.take<double>(satn * nimg * nw);
+        sat2 = ar.take<double>(satn * nimg * nw);
+        tstat = ar.take<double>(2 * (size_t)ntpl);
+        g = ar.take<float2>(half * pc);
+        gnyq = ar.take<float>((size_t)ny * pc);
+        xc = ar.take<float>(fpix * pc);
+        ncc = ar.take<float>(fpix * pc);
+        absncc = ar.take<float>(fpix * pc);
+        pval = ar.take<float>((size_t)nblk * pc);
+        pind = ar.take<int>((size_t)nblk * pc);
+        geom = ar.take<int>(4 * (size_t)pc);
+        gathered = ar.take<float>(fpix * pc);
+        pred = ar.take<unsigned>((size_t)pc);
+        msel = ar.take<SelState>(pc);
+    });
     if (rc) return rc;
-    float2* spec = ar.take<float2>(half * nsrc);
-    float2* nyq = ar.take<float2>((size_t)ny * nsrc);
-    float* nyq_rows = ar.take<float>((size_t)ny * nsrc);
-    RowSrc* srcs = ar.take<RowSrc>(nsrc);
-    double* roi_part = ar.take<double>((size_t)2 * ROI_SPLIT * nsrc);
-    int* pidx = ar.take<int>(3 * (size_t)npairs);
-    int* sidx = pidx + 2 * (size_t)npairs;
-    double* sat1 = ar.take<double>(satn * nimg * nw);
-    double* sat2 = ar.take<double>(satn * nimg * nw);
-    int* d_widx = ar.take<int>((size_t)ntpl);
-    double* tstat = ar.take<double>(2 * (size_t)ntpl);
-    float2* g = ar.take<float2>(half * pc);
-    float* gnyq = ar.take<float>((size_t)ny * pc);
-    float* xc = ar.take<float>(fpix * pc);
-    float* ncc = ar.take<float>(fpix * pc);
-    float* absncc = ar.take<float>(fpix * pc);
-    float* pval = ar.take<float>((size_t)nblk * pc);
-    int* pind = ar.take<int>((size_t)nblk * pc);
-    int* geom = ar.take<int>(4 * (size_t)pc);
-    float* gathered = ar.take<float>(fpix * pc);
-    unsigned* pred = ar.take<unsigned>((size_t)pc);
-    SelState* msel = reinterpret_cast<SelState*>(ar.take<unsigned>((size_t)SEL_WORDS * pc));
-
-    std::vector<RowSrc> h(nsrc);
-    for (int i = 0; i < nimg; ++i) h[i] = RowSrc{i, 0, img_h, 0, img_w, 0.f, 1.f, 0};
-    for (int k = 0; k < ntpl; ++k)
-        h[nimg + k] = RowSrc{tpl_frame[k], tpl_roi[4 * k], tpl_roi[4 * k + 1], tpl_roi[4 * k + 2], tpl_roi[4 * k + 3], 0.f, 1.f, 0};
-    std::vector<int> hp(3 * (size_t)npairs);
-    for (int i = 0; i < npairs; ++i) {
-        hp[i] = pair_img[i];
-        hp[npairs + i] = pair_tpl[i];
-        hp[2 * (size_t)npairs + i] = nimg + pair_tpl[i];  // templates sit after the images in `spec`
-    }
-    B4D_HIP(hipMemcpyAsync(srcs, h.data(), sizeof(RowSrc) * nsrc, hipMemcpyHostToDevice, st));
-    B4D_HIP(hipMemcpyAsync(pidx, hp.data(), sizeof(int) * hp.size(), hipMemcpyHostToDevice, st));
-    B4D_HIP(hipMemcpyAsync(d_widx, widx.data(), sizeof(int) * ntpl, hipMemcpyHostToDevice, st));
-    B4D_HIP(hipStreamSynchronize(st));
+    const int *sidx = pidx + 2 * (size_t)npairs, *d_widx = pidx + 3 * (size_t)npairs;
     // "opencv": the image is z-scored as a whole (tracking.py:157); "skimage": raw float32 image (tracking.py:166)
-    if (zscore_image && (rc = roi_stats(images, ny, nx, eps, srcs, nimg, roi_part, st))) return rc;
-    if ((rc = roi_stats(tpl_src, ny, nx, eps, srcs + nimg, ntpl, roi_part + (size_t)2 * ROI_SPLIT * nimg, st))) return rc;
-    hipLaunchKernelGGL(k_tpl_stats, dim3(ntpl), dim3(1024), 0, st, tpl_src, ny, nx, srcs + nimg, tstat);
+    if ((rc = track_sources(c, ny, nx, img_h, img_w, zscore_image != 0, 3, srcs, roi_part, pidx, st, widx))) return rc;
+    if ((rc = launch(k_tpl_stats, dim3(ntpl), dim3(1024), 0, st, tpl_src, ny, nx, srcs + nimg, tstat))) return rc;
     for (size_t j = 0; j < nw; ++j) {
         const size_t row_lds = sizeof(double) * 2 * ((size_t)nx + 1);
-        if ((rc = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_sat_rows), row_lds))) return rc;
-        hipLaunchKernelGGL(k_sat_rows, dim3(ny, nimg), dim3(256), row_lds, st, images, ny, nx, srcs, sat1 + j * satn * nimg,
-                           sat2 + j * satn * nimg, widths[j]);
-        hipLaunchKernelGGL(k_sat_cols, dim3((nx + 64) / 64, nimg), dim3(64), 0, st, ny, nx, sat1 + j * satn * nimg, sat2 + j * satn * nimg,
-                           heights[j]);
+        double *t1 = sat1 + j * satn * nimg, *t2 = sat2 + j * satn * nimg;
+        if ((rc = launch(k_sat_rows, dim3(ny, nimg), dim3(256), row_lds, st, images, ny, nx, srcs, t1, t2, widths[j]))) return rc;
+        if ((rc = launch(k_sat_cols, dim3((nx + 64) / 64, nimg), dim3(64), 0, st, ny, nx, t1, t2, heights[j]))) return rc;
     }
-    B4D_HIP(hipGetLastError());
-    const int fc = std::max(1, pl->chunk * 2);
-    for (int i0 = 0; i0 < nimg; i0 += fc) {
-        const int n = std::min(fc, nimg - i0);
-        if ((rc = forward_spectra(pl, images, srcs + i0, n, spec + half * i0, nyq_rows + (size_t)ny * i0, nyq + (size_t)ny * i0, st)))
-            return rc;
-    }
-    for (int k0 = 0; k0 < ntpl; k0 += fc) {
-        const int n = std::min(fc, ntpl - k0), o = nimg + k0;
-        if ((rc = forward_spectra(pl, tpl_src, srcs + o, n, spec + half * o, nyq_rows + (size_t)ny * o, nyq + (size_t)ny * o, st,
-                                  /*columns=*/false)))   // transformed per pair in k_col_prod<.., TPL>
-            return rc;
-    }
-    {
-        for (int p0 = 0; p0 < npairs; p0 += pc) {
-            const int np = std::min(pc, npairs - p0);
-            int r2 = product_inverse<false>(pl, spec, nyq, pidx + p0, sidx + p0, spec, nyq, np, g, gnyq, 0.f, 0u, st, srcs);
-            if (r2) return r2;
-            RowOutArgs ra{};
-            ra.g = g;
-            ra.gnyq = gnyq;
-            ra.out = xc;
-            ra.tw = pl->tw_x;
-            ra.scale = 1.0f / ((float)nx * (float)ny);
-            ra.ny = ny;
-            ra.ct_w = pl->ct_w;
-            if ((r2 = dispatch_c2r(pl, ra, np, st, C2R_OUT))) return r2;
-            NccArgs na{};
-            na.xc = xc;
-            na.sat1 = sat1;
-            na.sat2 = sat2;
-            na.pair_img = pidx + p0;
-            na.pair_tpl = pidx + npairs + p0;
-            na.tsrc = srcs + nimg;
-            na.tstat = tstat;
-            na.tpl_widx = d_widx;
-            na.nimg = nimg;
-            na.ncc = ncc;
-            na.absncc = absncc;
-            na.part_val = pval;
-            na.part_idx = pind;
-            na.geom = geom;
-            na.ny = ny;
-            na.nx = nx;
-            na.nblk = nblk;
-            na.img_h = img_h;
-            na.img_w = img_w;
-            const bool expect = g_opt_track_predict.load() != 0;   // "track_predict_bin" 0: the whole select on every map
-            na.pred = expect ? pred : nullptr;
-            na.sel = msel;
-            na.gathered = gathered;
-            B4D_HIP(hipMemsetAsync(msel, 0, sizeof(SelState) * (size_t)np, st));
-            if (expect) hipLaunchKernelGGL(k_ncc_sample, dim3(np), dim3(256), 0, st, na, pred);
-            hipLaunchKernelGGL(k_ncc_map, dim3(nblk, np), dim3(256), 0, st, na);
-            if (expect) hipLaunchKernelGGL(k_ncc_check, dim3((np + 63) / 64), dim3(64), 0, st, geom, pred, msel, np);
-            FinArgs fa{};
-            fa.mag = ncc;
-            fa.med_src = absncc;
-            fa.compact = xc;          // the correlation maps are consumed: their buffer serves as the median's scratch
-            fa.geom = geom;
-            fa.stride = fpix;
-            fa.part_val = pval;
-            fa.part_idx = pind;
-            fa.out = out + (size_t)p0 * 4;
-            fa.peak_ij = peak_ij ? peak_ij + (size_t)p0 * 2 : nullptr;
-            fa.ny = ny;
-            fa.nx = nx;
-            fa.nblk = nblk;
-            fa.subpixel = subpixel ? 1 : 0;   // the Newton step (2) is for displacement maps only
-            fa.eps = eps;
-            if (expect) {   // passes 2-3 of the select on the gathered bin; whoever is left takes the whole select on its map
-                FinArgs fg = fa;
-                fg.compact = gathered;
-                if ((rc = launch_track_fin2_checked(fg, msel, np, st))) return rc;
-            }
-            if ((rc = launch_track_fin_rest(fa, msel, np, st))) return rc;
-            B4D_HIP(hipGetLastError());
+    if ((rc = forward_spectra_sources(pl, images, nimg, tpl_src, ntpl, srcs, spec, nyq_rows, nyq, st))) return rc;
+    const bool expect = g_opt_track_predict.load() != 0;   // "track_predict_bin" 0: the whole select on every map
+    for (int p0 = 0; p0 < npairs; p0 += pc) {
+        const int np = std::min(pc, npairs - p0);
+        if ((rc = product_inverse<false>(pl, spec, nyq, pidx + p0, sidx + p0, spec, nyq, np, g, gnyq, 0.f, 0u, st, srcs))) return rc;
+        if ((rc = dispatch_c2r(pl, row_out_args(pl, g, gnyq, xc), np, st, C2R_OUT))) return rc;
+        NccArgs na{};
+        na.xc = xc;
+        na.sat1 = sat1;
+        na.sat2 = sat2;
+        na.pair_img = pidx + p0;
+        na.pair_tpl = pidx + npairs + p0;
+        na.tsrc = srcs + nimg;
+        na.tstat = tstat;
+        na.tpl_widx = d_widx;
+        na.nimg = nimg;
+        na.ncc = ncc;
+        na.absncc = absncc;
+        na.part_val = pval;
+        na.part_idx = pind;
+        na.geom = geom;
+        na.ny = ny;
+        na.nx = nx;
+        na.nblk = nblk;
+        na.img_h = img_h;
+        na.img_w = img_w;
+        na.pred = expect ? pred : nullptr;
+        na.sel = msel;
+        na.gathered = gathered;
+        B4D_HIP(hipMemsetAsync(msel, 0, sizeof(SelState) * (size_t)np, st));
+        if (expect && (rc = launch(k_ncc_sample, dim3(np), dim3(256), 0, st, na, pred))) return rc;
+        if ((rc = launch(k_ncc_map, dim3(nblk, np), dim3(256), 0, st, na))) return rc;
+        FinArgs fa = fin_args(c, p0, ncc, pval, pind, nblk, ny, nx);
+        fa.med_src = absncc;
+        fa.compact = xc;          // the correlation maps are consumed: their buffer serves as the median's scratch
+        fa.geom = geom;
+        fa.stride = fpix;
+        if (expect) {   // passes 2-3 of the select on the gathered bin; whoever is left takes the whole select on its map
+            FinArgs fg = fa;
+            fg.compact = gathered;
+            if ((rc = launch_track_fin2(fg, msel, 0u, pred, np, st))) return rc;
         }
+        if ((rc = launch_track_fin_rest(fa, msel, np, st))) return rc;
     }
     return B4D_OK;
 }

@@ -528,3 +528,104 @@ def test_template_matching_median_guess_is_only_a_route(gs, backend):
     for a, b in zip(out[1], out[0]):
         assert np.array_equal(a[0], b[0], equal_nan=True) and np.array_equal(a[1], b[1])
     assert np.all(np.rint(out[1][0][0][:8, 0]).reshape(4, 2) == sh[:, 0:1])
+
+
+def _xcorr_batch(a, b):
+    """b4d_xcorr2d on a batch (the Python layer takes one pair per call): remove_mean, no normalisation; on the cached plan."""
+    import torch
+
+    from barc4dip_amd import _device as D
+    from barc4dip_amd import _ffi
+
+    ta, _, _ = D.to_device_f32(a, ndim=(3,))
+    tb, _, _ = D.to_device_f32(b, ndim=(3,))
+    n, ny, nx = ta.shape
+    out = torch.empty((n, ny, nx), dtype=torch.float32, device=ta.device)
+    pl = _ffi.get_plan(ny, nx)
+    _ffi.check(_ffi.lib().b4d_xcorr2d(pl.handle, D.ptr(ta), D.ptr(tb), int(n), D.ptr(out), _ffi.REMOVE_MEAN, _ffi.stream_ptr()))
+    return out.cpu().numpy()
+
+
+def _pc_vs_oracle(key, res, pij, base, stack, rois, pair_img, pair_tpl, observe):
+    """rows of a phase_correlation_batch call (templates = `rois` of `base`) against the float64 oracle, under the bars `key`/*.
+    The frames are cast to float64 as in tests/test_gpu_tracking_edges.py: on white speckle the oracle's float32 path is itself
+    2.9e-4 px (64^2) and 7e-5 px (171 x 170) from its float64 path, the rounded DC bin that the device zeroes."""
+    from oracle import signal_np as S
+
+    for i, (t, k) in enumerate(zip(pair_img, pair_tpl)):
+        sl = (slice(rois[k][0], rois[k][1]), slice(rois[k][2], rois[k][3]))
+        tpl, img = base[sl].astype(np.float64), stack[t].astype(np.float64)
+        want = S.phase_correlation(tpl, img, slices_yx=sl)
+        mag = S.phase_correlation_map(tpl, img, slices_yx=sl)
+        assert (pij[i, 0], pij[i, 1]) == np.unravel_index(np.argmax(mag), mag.shape)
+        observe(f"{key}/sub_px", max(abs(res[i, 0] - want[0]), abs(res[i, 1] - want[1])), BARS[f"{key}/sub_px"])
+        observe(f"{key}/peak_rel", _rel(res[i, 2], want[2]), BARS[f"{key}/peak_rel"])
+        observe(f"{key}/snr_rel", _rel(res[i, 3], want[3]), BARS[f"{key}/snr_rel"])
+
+
+def test_workspace_regrowth_and_reuse_across_entry_points(gs, observe):
+    """One plan owns ONE tracking workspace, which every entry point carves for itself and grows when it is too small.  On the
+    cached 64 x 64 plan: a one-pair phase correlation (smallest layout), a 270-pair one (regrowth; two launch groups on two
+    lanes, each in its own slot of the per-group buffers), template matching with two template shapes, a cross-correlation of
+    three pairs -- then the four again in reverse order, in the workspace the largest of them left behind.  Every repeated call
+    returns rows and indices bit-identical to its first run, every first run stays within the bars of its entry point's own
+    tests.  The same short sequence (1, 12, 1 pairs) on the DFT-matrix route (171 x 170, 200 x 300) and the mixed-radix one
+    (228 x 228)."""
+    from barc4dip_amd import _ffi
+    from oracle import ncc_np as N
+    from oracle import signal_np as S
+
+    shifts = [(0, 0), (3, -5), (-7, 11)]
+    base, stack = synth.white_speckle_pairs((64, 64), shifts, seed=6464)
+    rois = [(y0, y0 + 31, x0, x0 + 31) for y0 in (0, 16, 33) for x0 in (0, 16, 33)]
+    img27, tpl27 = [t for t in range(3) for _ in rois], [k for _ in range(3) for k in range(9)]
+    many = 10
+    # b4d_phase_correlation: groups of pc_one = min(npairs, 4 x chunk) pairs, split over two lanes when npairs > pc_one / 2 and
+    # pc_one >= 64
+    pc_one = min(27 * many, 4 * _ffi.default_chunk(64, 64))
+    assert 27 * many > pc_one // 2 and pc_one >= 64
+    tm_rois = [(10, 31, 8, 29), (20, 35, 10, 41)]                          # 21 x 21 and 15 x 31, inside the frame at every shift
+    tm_img, tm_tpl = [t for t in range(3) for _ in tm_rois], [k for _ in range(3) for k in range(2)]
+    xa = np.stack([base] * 3)
+
+    calls = {
+        "one": lambda: gs.phase_correlation_batch(stack[1:2], base[None], [0], [rois[4]], [0], [0], return_peak_ij=True),
+        "many": lambda: gs.phase_correlation_batch(stack, base[None], [0] * 9, rois, img27 * many, tpl27 * many, return_peak_ij=True),
+        "ncc": lambda: gs.template_matching_batch(stack, base[None], [0, 0], tm_rois, tm_img, tm_tpl, return_peak_ij=True),
+        "xcorr": lambda: (_xcorr_batch(xa, stack),),
+    }
+    order = ["one", "many", "ncc", "xcorr"]
+    first = {name: calls[name]() for name in order}
+    for name in reversed(order):
+        again = calls[name]()
+        for a, b in zip(again, first[name]):
+            assert np.array_equal(a, b, equal_nan=True), name
+    res, pij = first["one"]
+    _pc_vs_oracle("all_routes", res, pij, base, stack[1:2], [rois[4]], [0], [0], observe)
+    res, pij = first["many"]
+    for r in range(1, many):                                              # the same pair gives the same row in every group and lane
+        assert np.array_equal(res[27 * r:27 * (r + 1)], res[:27]) and np.array_equal(pij[27 * r:27 * (r + 1)], pij[:27])
+    _pc_vs_oracle("all_routes", res, pij, base, stack, rois, img27, tpl27, observe)
+    for i in range(27):
+        assert (round(res[i, 0]), round(res[i, 1])) == shifts[img27[i]]
+    res, pij = first["ncc"]
+    for i, (t, k) in enumerate(zip(tm_img, tm_tpl)):
+        y0, y1, x0, x1 = tm_rois[k]
+        want = N.template_matching(base[y0:y1, x0:x1], stack[t], slices_yx=(slice(y0, y1), slice(x0, x1)), backend="opencv")
+        observe("ncc_mixed/sub_px", max(abs(res[i, 0] - want[0]), abs(res[i, 1] - want[1])), BARS["ncc_mixed/sub_px"])
+        observe("ncc_mixed/peak_abs", abs(res[i, 2] - want[2]), BARS["ncc_mixed/peak_abs"])
+        observe("ncc_mixed/snr_rel", _rel(res[i, 3], want[3]), BARS["ncc_mixed/snr_rel"])
+    for t in range(3):                                                    # the bar of test_xcorr2d
+        ref = np.real(S.xcorr2d(base.astype(np.float64), stack[t].astype(np.float64), remove_mean=True, normalize="none")[0])
+        assert float(np.max(np.abs(first["xcorr"][0][t] - ref)) / np.max(np.abs(ref))) < 1e-5
+
+    for shape in ((171, 170), (228, 228), (200, 300)):
+        H, W = shape
+        base, stack = synth.white_speckle_pairs(shape, shifts, seed=1000 * H + W)
+        rois = [synth.edge_roi(shape, (61, 61)), synth.edge_roi(shape, (41, 81))]
+        img12, tpl12 = [t for t in range(3) for _ in range(2)] * 2, [0, 1] * 6
+        sizes = {1: ([1], [1]), 12: (img12, tpl12)}
+        runs = [(n, gs.phase_correlation_batch(stack, base[None], [0, 0], rois, *sizes[n], return_peak_ij=True)) for n in (1, 12, 1)]
+        assert np.array_equal(runs[2][1][0], runs[0][1][0]) and np.array_equal(runs[2][1][1], runs[0][1][1]), shape
+        for n, (res, pij) in runs[:2]:
+            _pc_vs_oracle("general_sizes", res, pij, base, stack, rois, *sizes[n], observe)
