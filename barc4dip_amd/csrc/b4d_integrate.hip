@@ -61,6 +61,7 @@ struct WfGemm {
     const double* ly;
     const double* lx;
     double ihy2, ihx2;
+    const int* skip;   // per batch entry, may be null: a non-zero entry leaves its C untouched (maps that the weighted solver has frozen)
 };
 
 template <bool DIV>
@@ -71,6 +72,7 @@ __global__ void __launch_bounds__(256) k_wf_gemm(WfGemm g) {
     const int wr = wave >> 1, wc = wave & 1;
     const int li = lane & 31, lk = lane >> 5;
     const int m0 = blockIdx.y * WF_TILE, n0 = blockIdx.x * WF_TILE;
+    if (g.skip && g.skip[blockIdx.z]) return;
     const float* __restrict__ A = g.A + (long long)blockIdx.z * g.sA;
     const float* __restrict__ B = g.B + (long long)blockIdx.z * g.sB;
     float* __restrict__ Cm = g.C + (long long)blockIdx.z * g.sC;
@@ -135,7 +137,7 @@ struct WfFit {
 };
 constexpr int WF_FIT_THREADS = 1024;
 
-template <int NV>
+template <int NV, int NT = WF_FIT_THREADS>
 __device__ __forceinline__ void wf_block_sum(double (&v)[NV], double (*sh)[NV]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -149,7 +151,7 @@ __device__ __forceinline__ void wf_block_sum(double (&v)[NV], double (*sh)[NV]) 
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
             double s = 0.0;
-            for (int w = 0; w < WF_FIT_THREADS / 64; ++w) s += sh[w][k];
+            for (int w = 0; w < NT / 64; ++w) s += sh[w][k];
             v[k] = s;
         }
 }
@@ -300,13 +302,65 @@ static int wf_check_grid(int n, int ny, int nx) {
     return B4D_OK;
 }
 
-// Inverse Gram matrix of the six monomials on the (ny, nx) grid, float64.  The sums separate: sum u^a v^b = (sum_j u^a)(sum_i v^b).
-// A monomial that the grid cannot tell from the ones before it (a side of 1 or 2 nodes) is left out: its coefficient is 0.
-static void wf_gram_inverse(int ny, int nx, WfFit& f) {
+// Cholesky factor of the Gram matrix G of the six monomials and the solve with it, float64, for the host (unweighted fit: G
+// depends on the grid alone, the host keeps its inverse) and for one lane of the device (weighted fit: G from the weighted
+// moments of the map).  Monomials are taken in order; one whose remainder after the kept ones is below 1e-12 of itself is
+// dropped, and its coefficient is 0.
+struct WfChol {       // the device keeps it in LDS: the loops index it with run-time subscripts
+    double L[6][6];
+    double y[6];
+    bool kept[6];
+};
+
+__host__ __device__ inline void wf_gram_factor(const double (&G)[6][6], WfChol& f) {
+    for (int a = 0; a < 6; ++a) {
+        double d = G[a][a];
+        for (int b = 0; b < a; ++b) {
+            f.L[a][b] = 0.0;
+            if (!f.kept[b]) continue;
+            double s = G[a][b];
+            for (int c = 0; c < b; ++c)
+                if (f.kept[c]) s -= f.L[a][c] * f.L[b][c];
+            f.L[a][b] = s / f.L[b][b];
+            d -= f.L[a][b] * f.L[a][b];
+        }
+        f.kept[a] = d > 1e-12 * G[a][a] && G[a][a] > 0.0;
+        f.L[a][a] = f.kept[a] ? sqrt(d) : 0.0;
+    }
+}
+
+// x = G^-1 rhs on the kept set (G^-1 = L^-T L^-1: L y = rhs, L^T x = y), 0 for a dropped monomial
+__host__ __device__ inline void wf_gram_solve(WfChol& f, const double (&rhs)[6], double (&x)[6]) {
+    double* y = f.y;
+    for (int a = 0; a < 6; ++a) {
+        x[a] = 0.0;
+        if (!f.kept[a]) continue;
+        double s = rhs[a];
+        for (int c = 0; c < a; ++c)
+            if (f.kept[c]) s -= f.L[a][c] * y[c];
+        y[a] = s / f.L[a][a];
+    }
+    for (int a = 5; a >= 0; --a) {
+        if (!f.kept[a]) continue;
+        double s = y[a];
+        for (int c = a + 1; c < 6; ++c)
+            if (f.kept[c]) s -= f.L[c][a] * x[c];
+        x[a] = s / f.L[a][a];
+    }
+}
+
+// normalised coordinates of the fit: u = (j - cx) / max(cx, 1), v likewise
+static void wf_fit_coords(int ny, int nx, WfFit& f) {
     f.cx = 0.5 * (nx - 1);
     f.cy = 0.5 * (ny - 1);
     f.ixh = 1.0 / (nx > 1 ? f.cx : 1.0);
     f.iyh = 1.0 / (ny > 1 ? f.cy : 1.0);
+}
+
+// Inverse Gram matrix of the six monomials on the (ny, nx) grid, float64.  The sums separate: sum u^a v^b = (sum_j u^a)(sum_i v^b).
+// A monomial that the grid cannot tell from the ones before it (a side of 1 or 2 nodes) is left out: its coefficient is 0.
+static void wf_gram_inverse(int ny, int nx, WfFit& f) {
+    wf_fit_coords(ny, nx, f);
     double su[5] = {0, 0, 0, 0, 0}, sv[5] = {0, 0, 0, 0, 0};
     for (int j = 0; j < nx; ++j) {
         const double u = (j - f.cx) * f.ixh;
@@ -322,43 +376,390 @@ static void wf_gram_inverse(int ny, int nx, WfFit& f) {
     double G[6][6];
     for (int a = 0; a < 6; ++a)
         for (int b = 0; b < 6; ++b) G[a][b] = su[pu[a] + pu[b]] * sv[pv[a] + pv[b]];
-    // Cholesky of the kept monomials, in order; a monomial whose remainder after the kept ones is below 1e-12 of itself is dropped
-    bool kept[6];
-    double L[6][6] = {};
-    for (int a = 0; a < 6; ++a) {
-        double d = G[a][a];
-        for (int b = 0; b < a; ++b) {
-            if (!kept[b]) continue;
-            double s = G[a][b];
-            for (int c = 0; c < b; ++c)
-                if (kept[c]) s -= L[a][c] * L[b][c];
-            L[a][b] = s / L[b][b];
-            d -= L[a][b] * L[a][b];
-        }
-        kept[a] = d > 1e-12 * G[a][a] && G[a][a] > 0.0;
-        L[a][a] = kept[a] ? std::sqrt(d) : 0.0;
-    }
-    // G^-1 = L^-T L^-1 on the kept set: solve L y = e_b, L^T x = y for every kept column
+    WfChol ch;
+    wf_gram_factor(G, ch);
     for (int k = 0; k < 36; ++k) f.ginv[k] = 0.0;
-    for (int b = 0; b < 6; ++b) {
-        if (!kept[b]) continue;
-        double y[6] = {}, x[6] = {};
-        for (int a = 0; a < 6; ++a) {
-            if (!kept[a]) continue;
-            double s = a == b ? 1.0 : 0.0;
-            for (int c = 0; c < a; ++c)
-                if (kept[c]) s -= L[a][c] * y[c];
-            y[a] = s / L[a][a];
-        }
-        for (int a = 5; a >= 0; --a) {
-            if (!kept[a]) continue;
-            double s = y[a];
-            for (int c = a + 1; c < 6; ++c)
-                if (kept[c]) s -= L[c][a] * x[c];
-            x[a] = s / L[a][a];
-        }
+    for (int b = 0; b < 6; ++b) {     // column b of the inverse: the solve of the unit vector e_b
+        if (!ch.kept[b]) continue;
+        double rhs[6] = {}, x[6];
+        rhs[b] = 1.0;
+        wf_gram_solve(ch, rhs, x);
         for (int a = 0; a < 6; ++a) f.ginv[6 * a + b] = x[a];
     }
+}
+
+// ---- weighted / masked integration: preconditioned conjugate gradients on the weighted normal equations
+// A phi = b, started from 0, the unweighted DCT solve above as preconditioner.  Vectors are float32; every dot product is
+// accumulated in float64 per workgroup, written to the workspace and summed in index order by whoever needs it; alpha, beta and
+// the per-map state live on the device.  grid (nb, maps), nb = wf_pcg_blocks(plane) workgroups stride over a map.
+constexpr int WF_PCG_THREADS = 256;
+constexpr int WF_PCG_MAXBLOCKS = 256;   // partials per map and dot product
+constexpr int WF_PCG_CHECK = 4;         // the host reads the per-map flags every this many iterations
+
+struct WfPcgState {   // per map; iteration k reads slot k & 1 and writes the other, so no workgroup reads what another writes
+    double rz;        // r . z of the current search direction
+    double rr;        // |r|^2 of the recurrence residual
+    int iters;
+    int frozen;
+};
+
+struct WfPcg {
+    float *weff, *cy, *cx, *r, *p, *qz, *t;   // (n, ny, nx) each: node weights, edge coefficients wy/hy^2 and wx/hx^2, PCG vectors
+    double *bb, *part_a, *part_b, *part_c;    // (n), 3 x (n, nb): |b|^2; partials of |b|^2 then p.q; of r.r; of r.z
+    WfPcgState* state;                        // (2, n)
+    int *badpq, *flags;                       // (n): p.q was not finite and positive; frozen, for the host
+    int n, ny, nx, nb;
+    double tol2;                              // rtol^2
+};
+
+static int wf_pcg_blocks(long long plane) {
+    const long long b = (plane + WF_PCG_THREADS - 1) / WF_PCG_THREADS;
+    return (int)(b < WF_PCG_MAXBLOCKS ? b : WF_PCG_MAXBLOCKS);
+}
+
+static size_t wf_align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// carves the caller's workspace; returns the bytes used (base == nullptr: size only)
+static size_t wf_pcg_layout(char* base, int n, int ny, int nx, WfPcg& g) {
+    const size_t plane = (size_t)ny * nx, fv = wf_align256((size_t)n * plane * sizeof(float));
+    const int nb = wf_pcg_blocks((long long)plane);
+    const size_t dv = wf_align256((size_t)n * nb * sizeof(double)), sv = wf_align256((size_t)n * sizeof(double));
+    size_t o = 0;
+    float** fp[7] = {&g.weff, &g.cy, &g.cx, &g.r, &g.p, &g.qz, &g.t};
+    for (auto f : fp) {
+        *f = (float*)(base + o);
+        o += fv;
+    }
+    g.bb = (double*)(base + o), o += sv;
+    double** dp[3] = {&g.part_a, &g.part_b, &g.part_c};
+    for (auto d : dp) {
+        *d = (double*)(base + o);
+        o += dv;
+    }
+    g.state = (WfPcgState*)(base + o), o += wf_align256(2 * (size_t)n * sizeof(WfPcgState));
+    g.badpq = (int*)(base + o), o += wf_align256((size_t)n * sizeof(int));
+    g.flags = (int*)(base + o), o += wf_align256((size_t)n * sizeof(int));
+    g.n = n, g.ny = ny, g.nx = nx, g.nb = nb;
+    return o;
+}
+
+// sum of the nb partials of one map, in index order (every lane the same chain, so every workgroup gets the same bits)
+__device__ __forceinline__ double wf_sum_partials(const double* __restrict__ part, int map, int nb) {
+    double s = 0.0;
+    for (int b = 0; b < nb; ++b) s += part[(size_t)map * nb + b];
+    return s;
+}
+
+// effective weight of a node: 0 unless the weight is finite and positive and both slopes are finite
+__device__ __forceinline__ float wf_weff(const float* __restrict__ w, const float* __restrict__ gy, const float* __restrict__ gx, int e) {
+    const float a = w[e];
+    return (a > 0.f && isfinite(a) && isfinite(gy[e]) && isfinite(gx[e])) ? a : 0.f;
+}
+
+// harmonic mean 2ab / (a + b) of two node weights, 0 if either is 0
+__device__ __forceinline__ float wf_hmean(float a, float b) { return (a > 0.f && b > 0.f) ? 2.f * a * (b / (a + b)) : 0.f; }
+
+// once per call: effective weights, edge coefficients, b, x = 0, partials of |b|^2.  Slopes of weight-0 nodes only pass through
+// isfinite: their edges have coefficient 0 and are selected away, not multiplied.  w_stride 0 shares the weights across maps.
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wsetup(const float* __restrict__ gy, const float* __restrict__ gx,
+                                                              const float* __restrict__ w, long long w_stride, float ihy, float ihx,
+                                                              WfPcg g, float* __restrict__ x) {
+    __shared__ double sh[WF_PCG_THREADS / 64][1];
+    const int map = blockIdx.y, ny = g.ny, nx = g.nx, plane = ny * nx;
+    const size_t fo = (size_t)map * plane;
+    const float* __restrict__ my = gy + fo;
+    const float* __restrict__ mx = gx + fo;
+    const float* __restrict__ mw = w + (long long)map * w_stride;
+    double s[1] = {0.0};
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS) {
+        const int i = e / nx, j = e % nx;
+        const float w0 = wf_weff(mw, my, mx, e);
+        const float hd = i + 1 < ny ? wf_hmean(w0, wf_weff(mw, my, mx, e + nx)) : 0.f;
+        const float hu = i > 0 ? wf_hmean(w0, wf_weff(mw, my, mx, e - nx)) : 0.f;
+        const float hr = j + 1 < nx ? wf_hmean(w0, wf_weff(mw, my, mx, e + 1)) : 0.f;
+        const float hl = j > 0 ? wf_hmean(w0, wf_weff(mw, my, mx, e - 1)) : 0.f;
+        float by = 0.f, bx = 0.f;
+        if (hu > 0.f) by += hu * (0.5f * (my[e - nx] + my[e]));
+        if (hd > 0.f) by -= hd * (0.5f * (my[e] + my[e + nx]));
+        if (hl > 0.f) bx += hl * (0.5f * (mx[e - 1] + mx[e]));
+        if (hr > 0.f) bx -= hr * (0.5f * (mx[e] + mx[e + 1]));
+        const float b = by * ihy + bx * ihx;
+        g.weff[fo + e] = w0;
+        g.cy[fo + e] = hd * ihy * ihy;
+        g.cx[fo + e] = hr * ihx * ihx;
+        g.r[fo + e] = b;
+        x[fo + e] = 0.f;
+        s[0] += (double)b * (double)b;
+    }
+    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
+}
+
+// q = A p (weighted 5-point operator; the last row of cy and the last column of cx are 0), partials of p . q
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wapply(WfPcg g, int slot) {
+    __shared__ double sh[WF_PCG_THREADS / 64][1];
+    const int map = blockIdx.y;
+    if (g.state[(size_t)slot * g.n + map].frozen) return;
+    const int ny = g.ny, nx = g.nx, plane = ny * nx;
+    const size_t fo = (size_t)map * plane;
+    const float* __restrict__ p = g.p + fo;
+    const float* __restrict__ cy = g.cy + fo;
+    const float* __restrict__ cx = g.cx + fo;
+    double s[1] = {0.0};
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS) {
+        const int i = e / nx, j = e % nx;
+        const float pc = p[e];
+        float a = 0.f;
+        if (i > 0) a += cy[e - nx] * (pc - p[e - nx]);
+        if (i + 1 < ny) a += cy[e] * (pc - p[e + nx]);
+        if (j > 0) a += cx[e - 1] * (pc - p[e - 1]);
+        if (j + 1 < nx) a += cx[e] * (pc - p[e + 1]);
+        g.qz[fo + e] = a;
+        s[0] += (double)pc * (double)a;
+    }
+    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
+}
+
+// alpha = r.z / p.q in float64; x += alpha p, r -= alpha q, partials of r . r.  A p.q that is not finite and positive stops the map.
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wupdate(WfPcg g, int slot, float* __restrict__ x) {
+    __shared__ double sh[WF_PCG_THREADS / 64][1];
+    const int map = blockIdx.y;
+    const WfPcgState st = g.state[(size_t)slot * g.n + map];
+    if (st.frozen) return;
+    const double pq = wf_sum_partials(g.part_a, map, g.nb);
+    if (!(pq > 0.0 && isfinite(pq))) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) g.badpq[map] = 1;
+        return;
+    }
+    const float alpha = (float)(st.rz / pq);
+    const int plane = g.ny * g.nx;
+    const size_t fo = (size_t)map * plane;
+    double s[1] = {0.0};
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS) {
+        x[fo + e] = fmaf(alpha, g.p[fo + e], x[fo + e]);
+        const float r = fmaf(-alpha, g.qz[fo + e], g.r[fo + e]);
+        g.r[fo + e] = r;
+        s[0] += (double)r * (double)r;
+    }
+    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    if (threadIdx.x == 0) g.part_b[(size_t)map * g.nb + blockIdx.x] = s[0];
+}
+
+// partials of r . z (z = M r sits in qz after the four products)
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wdot(WfPcg g, int slot, int first) {
+    __shared__ double sh[WF_PCG_THREADS / 64][1];
+    const int map = blockIdx.y;
+    if (!first && (g.state[(size_t)slot * g.n + map].frozen || g.badpq[map])) return;
+    const int plane = g.ny * g.nx;
+    const size_t fo = (size_t)map * plane;
+    double s[1] = {0.0};
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS)
+        s[0] += (double)g.r[fo + e] * (double)g.qz[fo + e];
+    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    if (threadIdx.x == 0) g.part_c[(size_t)map * g.nb + blockIdx.x] = s[0];
+}
+
+// state of the next iteration and p = z + beta p.  first: state from |b|^2 and r.z, p = z.  A map is frozen when b = 0 (or not
+// finite), when p.q was bad, or when |r| <= rtol |b|; a frozen map is not touched again, so no 0/0 is ever formed for it.
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wdirection(WfPcg g, int slot, int first) {
+    const int map = blockIdx.y;
+    WfPcgState st;
+    double beta = 0.0;
+    if (first) {
+        const double bb = wf_sum_partials(g.part_a, map, g.nb);
+        st.rr = bb;
+        st.iters = 0;
+        st.frozen = !(bb > 0.0 && isfinite(bb));
+        st.rz = st.frozen ? 0.0 : wf_sum_partials(g.part_c, map, g.nb);
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            g.bb[map] = bb;
+            g.badpq[map] = 0;
+        }
+    } else {
+        st = g.state[(size_t)slot * g.n + map];
+        if (!st.frozen) {
+            if (g.badpq[map]) {
+                st.frozen = 1;
+            } else {
+                st.rr = wf_sum_partials(g.part_b, map, g.nb);
+                st.iters += 1;
+                if (st.rr <= g.tol2 * g.bb[map] || !isfinite(st.rr)) {
+                    st.frozen = 1;
+                } else {
+                    const double rz = wf_sum_partials(g.part_c, map, g.nb);
+                    beta = st.rz > 0.0 ? rz / st.rz : 0.0;
+                    st.rz = rz;
+                }
+            }
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        g.state[(size_t)(first ? 0 : slot ^ 1) * g.n + map] = st;
+        g.flags[map] = st.frozen;
+    }
+    if (st.frozen) return;
+    const float bt = (float)beta;
+    const int plane = g.ny * g.nx;
+    const size_t fo = (size_t)map * plane;
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS)
+        g.p[fo + e] = first ? g.qz[fo + e] : fmaf(bt, g.p[fo + e], g.qz[fo + e]);
+}
+
+// iterations, final |r| / |b| (0 for b = 0), and NaN at the weight-0 nodes when asked
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wfinish(WfPcg g, int slot, int nan_invalid, float* __restrict__ x,
+                                                               int* __restrict__ iterations, double* __restrict__ residual) {
+    const int map = blockIdx.y;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const WfPcgState st = g.state[(size_t)slot * g.n + map];
+        const double bb = g.bb[map];
+        iterations[map] = st.iters;
+        residual[map] = (bb > 0.0 && isfinite(bb)) ? sqrt(st.rr / bb) : 0.0;
+    }
+    if (!nan_invalid) return;
+    const int plane = g.ny * g.nx;
+    const size_t fo = (size_t)map * plane;
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS)
+        if (!(g.weff[fo + e] > 0.f)) x[fo + e] = __builtin_nanf("");
+}
+
+// ---- weighted fit: the 15 weighted monomial moments sum w u^a v^b (a + b <= 4) and the six weighted right-hand moments of a map
+// in float64, one workgroup per map; lane 0 forms the Gram matrix and solves it with the factorisation and drop rule of the unweighted fit.
+// A node counts only if its weight is finite and positive, so a NaN in the map at a weight-0 node is never read into a sum.
+constexpr int WF_WFIT_THREADS = 1024;
+__host__ __device__ constexpr int wf_midx(int a, int b) { return 5 * a - a * (a - 1) / 2 + b; }   // (a, b), a + b <= 4 -> 0 .. 14
+
+__device__ __forceinline__ float wf_fit_weight(const float* __restrict__ w, int e) {
+    const float a = w[e];
+    return (a > 0.f && isfinite(a)) ? a : 0.f;
+}
+
+// wf_block_sum for many sums: lane k adds column k of the wave results (same order, wave 0 first), so that thread 0 does not hold
+// NV x waves loads in registers at once
+template <int NV, int NT>
+__device__ __forceinline__ void wf_block_sum_columns(double (&v)[NV], double (*sh)[NV]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+        if (lane == 0) sh[wave][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < NV) {
+        double s = 0.0;
+        for (int w = 0; w < NT / 64; ++w) s += sh[w][threadIdx.x];
+        sh[0][threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = sh[0][k];
+}
+
+__global__ void __launch_bounds__(WF_WFIT_THREADS) k_wf_poly2_wmoments(const float* __restrict__ phi, const float* __restrict__ w,
+                                                                      long long w_stride, int ny, int nx, WfFit f,
+                                                                      double* __restrict__ coeff) {
+    __shared__ double sh[WF_WFIT_THREADS / 64][21];
+    __shared__ struct {
+        double G[6][6], rhs[6], c[6];
+        WfChol ch;
+    } fit;
+    const int npix = ny * nx;
+    const float* __restrict__ p = phi + (size_t)blockIdx.x * npix;
+    const float* __restrict__ mw = w + (long long)blockIdx.x * w_stride;
+    double s[21];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) s[k] = 0.0;
+    for (int e = threadIdx.x; e < npix; e += WF_WFIT_THREADS) {
+        const float wf = wf_fit_weight(mw, e);
+        if (!(wf > 0.f)) continue;
+        const int i = e / nx, j = e % nx;
+        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh, wd = (double)wf, x = wd * (double)p[e];
+        double up[5], vp[5];
+        up[0] = vp[0] = 1.0;
+#pragma unroll
+        for (int a = 1; a < 5; ++a) up[a] = up[a - 1] * u, vp[a] = vp[a - 1] * v;
+#pragma unroll
+        for (int a = 0; a < 5; ++a)
+#pragma unroll
+            for (int b = 0; a + b < 5; ++b) s[wf_midx(a, b)] += wd * up[a] * vp[b];
+        s[15] += x;
+        s[16] += u * x;
+        s[17] += v * x;
+        s[18] += u * u * x;
+        s[19] += u * v * x;
+        s[20] += v * v * x;
+    }
+    wf_block_sum_columns<21, WF_WFIT_THREADS>(s, sh);
+    if (threadIdx.x == 0) {
+        constexpr int pu[6] = {0, 1, 0, 2, 1, 0}, pv[6] = {0, 0, 1, 0, 1, 2};
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            fit.rhs[a] = s[15 + a];
+#pragma unroll
+            for (int b = 0; b < 6; ++b) fit.G[a][b] = s[wf_midx(pu[a] + pu[b], pv[a] + pv[b])];
+        }
+        wf_gram_factor(fit.G, fit.ch);
+        wf_gram_solve(fit.ch, fit.rhs, fit.c);
+        for (int a = 0; a < 6; ++a) coeff[6 * (size_t)blockIdx.x + a] = fit.c[a];
+    }
+}
+
+// residual as k_wf_poly2_residual; rms = weighted population standard deviation sqrt(sum w r^2 / sum w - (sum w r / sum w)^2) over
+// the nodes of positive weight (NaN if there is none); weight-0 nodes get NaN when nan_invalid, else the same subtraction
+__global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_wresidual(const float* phi, const float* __restrict__ w, long long w_stride,
+                                                                       int ny, int nx, WfFit f, const double* __restrict__ coeff,
+                                                                       unsigned mask, double scale, int nan_invalid, float* residual,
+                                                                       double* __restrict__ rms) {
+    __shared__ double sh[WF_FIT_THREADS / 64][3];
+    const int npix = ny * nx;
+    const float* p = phi + (size_t)blockIdx.x * npix;
+    const float* __restrict__ mw = w + (long long)blockIdx.x * w_stride;
+    float* q = residual + (size_t)blockIdx.x * npix;
+    double c[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) c[k] = ((mask >> k) & 1u) ? coeff[6 * (size_t)blockIdx.x + k] : 0.0;
+    double s[3] = {0.0, 0.0, 0.0};
+    for (int e = threadIdx.x; e < npix; e += WF_FIT_THREADS) {
+        const float wf = wf_fit_weight(mw, e);
+        if (!(wf > 0.f) && nan_invalid) {
+            q[e] = __builtin_nanf("");
+            continue;
+        }
+        const int i = e / nx, j = e % nx;
+        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh;
+        const double fit = c[0] + u * (c[1] + c[3] * u + c[4] * v) + v * (c[2] + c[5] * v);
+        const float out = (float)(scale * ((double)p[e] - fit));
+        q[e] = out;
+        if (wf > 0.f) {
+            s[0] += (double)wf;
+            s[1] += (double)wf * (double)out;
+            s[2] += (double)wf * (double)out * (double)out;
+        }
+    }
+    wf_block_sum<3>(s, sh);
+    if (threadIdx.x == 0) {
+        const double mean = s[0] > 0.0 ? s[1] / s[0] : 0.0;
+        rms[blockIdx.x] = s[0] > 0.0 ? sqrt(fmax(0.0, s[2] / s[0] - mean * mean)) : __builtin_nan("");
+    }
+}
+
+// z = M rhs: the four products of the DCT Poisson solve; `out` may be `rhs` itself, `scratch` is distinct from both; maps with a
+// non-zero skip[] entry (may be null) are left out
+static void wf_poisson(const WfBasis* by, const WfBasis* bx, const float* rhs, float* scratch, float* out, int n, int ny, int nx,
+                       double hy, double hx, const int* skip, hipStream_t st) {
+    const long long plane = (long long)ny * nx;
+    const dim3 grid((nx + WF_TILE - 1) / WF_TILE, (ny + WF_TILE - 1) / WF_TILE, n);
+    const double ihy2 = 1.0 / (hy * hy), ihx2 = 1.0 / (hx * hx);
+    const WfGemm p1{rhs, bx->CT, scratch, ny, nx, nx, plane, 0, plane, nullptr, nullptr, 0.0, 0.0, skip};        // A1 = r . Cx^T
+    const WfGemm p2{by->C, scratch, out, ny, nx, ny, 0, plane, plane, by->lam, bx->lam, ihy2, ihx2, skip};       // P = (Cy . A1) / Lambda
+    const WfGemm p3{out, bx->C, scratch, ny, nx, nx, plane, 0, plane, nullptr, nullptr, 0.0, 0.0, skip};         // A2 = P . Cx
+    const WfGemm p4{by->CT, scratch, out, ny, nx, ny, 0, plane, plane, nullptr, nullptr, 0.0, 0.0, skip};        // phi = Cy^T . A2
+    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p1);
+    hipLaunchKernelGGL(k_wf_gemm<true>, grid, dim3(256), 0, st, p2);
+    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p3);
+    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p4);
 }
 
 }  // namespace b4d
@@ -385,16 +786,7 @@ extern "C" int b4d_integrate_gradient(const float* gy, const float* gx, int n, i
     if (const int rc = wf_basis(nx, ny, &bx)) return rc;
     hipLaunchKernelGGL(k_wf_rhs, dim3((unsigned)((plane + 255) / 256), n), dim3(256), 0, st, gy, gx, ny, nx, (float)(1.0 / hy),
                        (float)(1.0 / hx), out);
-    const dim3 grid((nx + WF_TILE - 1) / WF_TILE, (ny + WF_TILE - 1) / WF_TILE, n);
-    const double ihy2 = 1.0 / (hy * hy), ihx2 = 1.0 / (hx * hx);
-    const WfGemm p1{out, bx->CT, ws, ny, nx, nx, plane, 0, plane, nullptr, nullptr, 0.0, 0.0};          // A1 = r . Cx^T
-    const WfGemm p2{by->C, ws, out, ny, nx, ny, 0, plane, plane, by->lam, bx->lam, ihy2, ihx2};         // P = (Cy . A1) / Lambda
-    const WfGemm p3{out, bx->C, ws, ny, nx, nx, plane, 0, plane, nullptr, nullptr, 0.0, 0.0};           // A2 = P . Cx
-    const WfGemm p4{by->CT, ws, out, ny, nx, ny, 0, plane, plane, nullptr, nullptr, 0.0, 0.0};          // phi = Cy^T . A2
-    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p1);
-    hipLaunchKernelGGL(k_wf_gemm<true>, grid, dim3(256), 0, st, p2);
-    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p3);
-    hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p4);
+    wf_poisson(by, bx, out, ws, out, n, ny, nx, hy, hx, nullptr, st);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
@@ -413,6 +805,81 @@ extern "C" int b4d_poly2_fit(const float* w, int n, int ny, int nx, unsigned rem
     if (residual)
         hipLaunchKernelGGL(k_wf_poly2_residual, dim3(n), dim3(WF_FIT_THREADS), 0, st, w, ny, nx, f, (const double*)coeff, remove_mask,
                            scale, residual, rms);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+
+extern "C" size_t b4d_integrate_weighted_workspace_bytes(int n, int ny, int nx) {
+    if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
+    WfPcg g;
+    return wf_pcg_layout(nullptr, n, ny, nx, g);
+}
+
+extern "C" int b4d_integrate_gradient_weighted(const float* gy, const float* gx, const float* w, long long w_stride, int n, int ny,
+                                               int nx, double hy, double hx, double rtol, int max_iter, int nan_invalid,
+                                               void* workspace, float* out, int* iterations, double* residual, void* stream) {
+    if (!gy || !gx || !w || !workspace || !out || !iterations || !residual) return fail(B4D_EINVAL, "null argument");
+    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
+    if (!(hy > 0.0 && hx > 0.0 && std::isfinite(hy) && std::isfinite(hx)))
+        return fail(B4D_EINVAL, "grid spacings must be finite and > 0");
+    const long long plane = (long long)ny * nx;
+    if (w_stride != 0 && w_stride != plane) return fail(B4D_EINVAL, "w_stride is 0 (shared weights) or ny * nx (per map)");
+    if (!(rtol >= 0.0 && std::isfinite(rtol))) return fail(B4D_EINVAL, "rtol must be finite and >= 0");
+    if (max_iter < 0) return fail(B4D_EINVAL, "max_iter must be >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    WfPcg g;
+    wf_pcg_layout((char*)workspace, n, ny, nx, g);
+    g.tol2 = rtol * rtol;
+    std::lock_guard<std::mutex> lk(wf_mutex());     // basis pointers stay valid until the launches below are queued
+    const WfBasis *by = nullptr, *bx = nullptr;
+    if (const int rc = wf_basis(ny, ny, &by)) return rc;
+    if (const int rc = wf_basis(nx, ny, &bx)) return rc;
+    const dim3 grid(g.nb, n), block(WF_PCG_THREADS);
+    hipLaunchKernelGGL(k_wf_wsetup, grid, block, 0, st, gy, gx, w, w_stride, (float)(1.0 / hy), (float)(1.0 / hx), g, out);
+    wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, nullptr, st);
+    hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, 0, 1);
+    hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, 0, 1);
+    std::vector<int> flags(n);
+    int done = 0;
+    while (done < max_iter) {
+        const int slot = done & 1;
+        hipLaunchKernelGGL(k_wf_wapply, grid, block, 0, st, g, slot);
+        hipLaunchKernelGGL(k_wf_wupdate, grid, block, 0, st, g, slot, out);
+        wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, g.flags, st);      // frozen maps cost no products
+        hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, slot, 0);
+        hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, slot, 0);
+        ++done;
+        if (done % WF_PCG_CHECK == 0 && done < max_iter) {   // every map frozen: stop early (one small copy and a wait)
+            B4D_HIP(hipMemcpyAsync(flags.data(), g.flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+            B4D_HIP(hipStreamSynchronize(st));
+            bool all = true;
+            for (int m = 0; m < n && all; ++m) all = flags[m] != 0;
+            if (all) break;
+        }
+    }
+    hipLaunchKernelGGL(k_wf_wfinish, grid, block, 0, st, g, done & 1, nan_invalid, out, iterations, residual);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+
+extern "C" int b4d_poly2_fit_weighted(const float* w_map, const float* weights, long long weight_stride, int n, int ny, int nx,
+                                      unsigned remove_mask, double scale, int nan_invalid, double* coeff, float* residual, double* rms,
+                                      void* stream) {
+    if (!w_map || !weights || !coeff) return fail(B4D_EINVAL, "null argument");
+    if ((residual == nullptr) != (rms == nullptr)) return fail(B4D_EINVAL, "residual and rms go together (both or neither)");
+    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
+    if (weight_stride != 0 && weight_stride != (long long)ny * nx)
+        return fail(B4D_EINVAL, "weight_stride is 0 (shared weights) or ny * nx (per map)");
+    if (remove_mask > 63u) return fail(B4D_EINVAL, "remove_mask has six bits");
+    if (!std::isfinite(scale)) return fail(B4D_EINVAL, "scale must be finite");
+    hipStream_t st = (hipStream_t)stream;
+    WfFit f;
+    wf_fit_coords(ny, nx, f);
+    for (double& v : f.ginv) v = 0.0;
+    hipLaunchKernelGGL(k_wf_poly2_wmoments, dim3(n), dim3(WF_WFIT_THREADS), 0, st, w_map, weights, weight_stride, ny, nx, f, coeff);
+    if (residual)
+        hipLaunchKernelGGL(k_wf_poly2_wresidual, dim3(n), dim3(WF_FIT_THREADS), 0, st, w_map, weights, weight_stride, ny, nx, f,
+                           (const double*)coeff, remove_mask, scale, nan_invalid, residual, rms);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }

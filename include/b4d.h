@@ -327,6 +327,35 @@ int b4d_integrate_gradient(const float* gy, const float* gx, int n, int ny, int 
 int b4d_poly2_fit(const float* w, int n, int ny, int nx, unsigned remove_mask, double scale, double* coeff, float* residual,
                   double* rms, void* stream);
 
+/* Weighted and masked wavefront reconstruction.
+ * b4d_integrate_gradient_weighted: as b4d_integrate_gradient with a weight w >= 0 per node.  A node whose weight is not finite
+ *   and positive, or whose gy or gx is not finite, has weight 0 and its slopes are never read into a result.  Edge weights are
+ *   the harmonic mean 2ab / (a + b) of the two node weights (0 if either is 0); phi minimises
+ *     sum wy ((phi[i+1][j] - phi[i][j]) / hy - gbar_y[i][j])^2 + sum wx ((phi[i][j+1] - phi[i][j]) / hx - gbar_x[i][j])^2.
+ *   Solved by conjugate gradients from phi = 0, preconditioned with the unweighted DCT solve, which fixes the gauge: the
+ *   minimiser of smallest unweighted Laplacian energy with zero mean over the grid (disconnected pieces are levelled against
+ *   each other, not measured; weight-0 nodes are filled harmonically).  float32 vectors; dot products, alpha and beta in float64
+ *   on the device, reduced in a fixed order, so a map gives the same bits alone and inside any batch.  A map stops when its
+ *   recurrence residual |r| <= rtol |b|, when b = 0, or when p.Ap is not finite and positive; the call stops after max_iter
+ *   iterations or when every map has stopped (the host reads one int per map every 4 iterations: the call waits for `stream`).
+ *   w: DEVICE float32, (n, ny, nx) with w_stride = ny * nx or one (ny, nx) map shared by the batch with w_stride = 0.
+ *   nan_invalid != 0 writes NaN at the weight-0 nodes of out, else they keep the harmonic fill.  iterations: DEVICE (n) int32;
+ *   residual: DEVICE (n) float64, the final |r| / |b| (0 for b = 0).  workspace: DEVICE,
+ *   b4d_integrate_weighted_workspace_bytes(n, ny, nx) bytes (0 for an unsupported shape), 256-byte aligned; after the call its
+ *   first n * ny * nx floats hold the effective node weights.  Limits and errors as b4d_integrate_gradient.
+ * b4d_poly2_fit_weighted: b4d_poly2_fit with node weights (layout as above; not finite and positive counts as 0, and the map is
+ *   not read there): the weighted moments of the map in float64 on the device, where one lane solves the 6 x 6 system with the
+ *   factorisation and drop rule of the unweighted fit (a map with a single valid row gets no v terms).  u, v are the full-grid
+ *   coordinates.  rms = sqrt(sum w r^2 / sum w - (sum w r / sum w)^2), NaN without a valid node; nan_invalid != 0 writes NaN at
+ *   the weight-0 nodes of residual. */
+size_t b4d_integrate_weighted_workspace_bytes(int n, int ny, int nx);
+int b4d_integrate_gradient_weighted(const float* gy, const float* gx, const float* w, long long w_stride, int n, int ny, int nx,
+                                    double hy, double hx, double rtol, int max_iter, int nan_invalid, void* workspace, float* out,
+                                    int* iterations, double* residual, void* stream);
+int b4d_poly2_fit_weighted(const float* w_map, const float* weights, long long weight_stride, int n, int ny, int nx,
+                           unsigned remove_mask, double scale, int nan_invalid, double* coeff, float* residual, double* rms,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
