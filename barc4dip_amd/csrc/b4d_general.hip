@@ -1,5 +1,5 @@
 // b4d_general.hip -- general-length 2-D transforms: any 2 <= ny, nx <= 512 as dense DFT-matrix products; larger frames
-// whose sides split as P * A * B through the fused in-LDS mixed-radix row transform of b4d_wiener.hip (plan->large).
+// whose sides split as P * A * B through the fused in-LDS mixed-radix row transform of b4d_pm.hip (plan->large).
 //
 // The aggregators of barc4dip evaluate every metric on 3x3 tiles or 9x9 sub-tiles (metrics/common.py:75-106,
 // 278-378): 170/171-pixel tiles at 512^2, 227/228 at 2048^2 -- sizes with large prime factors (19, 227).  For these
@@ -9,6 +9,7 @@
 // The product kernel is a plain LDS-tiled complex GEMM on the vector ALUs (64x64 tile, 4x4 register block);
 // moving it to v_mfma_f32_32x32x2_f32 is listed in DESIGN.md §8.
 #include "b4d_fft2d.hpp"
+#include "b4d_pm.hpp"
 #include "b4d_wiener_mr.hpp"
 
 namespace b4d {

@@ -1,6 +1,7 @@
 // b4d_kernels.hip -- C ABI (include/b4d.h) of the FFT -> PSD -> autocorrelation hot path
 // (SURVEY.md §8 rows a1-a5).  Kernels live in b4d_fft2d.hpp / b4d_fft.hpp.
 #include "b4d_passes.hpp"
+#include "b4d_pm.hpp"
 #include "b4d_wiener_mr.hpp"
 
 #include <cstring>

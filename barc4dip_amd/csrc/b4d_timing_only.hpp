@@ -6,7 +6,7 @@
 // tests/test_cabi.py refuses -- so that a wrong-result build can never pass for the product library.
 #pragma once
 #if !defined(B4D_TIMING_ONLY) && (defined(B4D_EXP_NOTW) || defined(B4D_EXP_NOXCHG) || defined(B4D_EXP_NOBAR) || \
-                                  defined(B4D_EXP_PM_SKIP23) || defined(B4D_EXP_PM_NOTAB) || defined(B4D_EXP_PM_PACKED))
+                                  defined(B4D_EXP_PM_SKIP23) || defined(B4D_EXP_PM_NOTAB))
 #error "B4D_EXP_* are timing-only switches: build them with -DB4D_TIMING_ONLY (libb4d_alt.so), never into libb4d.so"
 #endif
 #ifdef B4D_TIMING_ONLY

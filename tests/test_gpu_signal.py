@@ -464,11 +464,16 @@ def test_complex_fft2d_and_ifft2d(gs, shape):
     assert nerr(gs.fft.ifft2d(gs.fft2d(real)[0]).real, real) < TOL
 
 
-@pytest.mark.parametrize("shape", [(1072, 536), (1197, 640), (1540, 1326), (1326, 1072), (3000, 520), (8192, 64)])
+@pytest.mark.parametrize("shape", [(1072, 536), (1197, 640), (1540, 1326), (1326, 1072), (3000, 520), (8192, 64), (5, 3024)])
 def test_fused_transform_factorisations(gs, shape):
     """Sides chosen for the corner cases of the fused row transform: a prime M (1072 = 16 * 67: A = 67, B = 1, table-free
-    path), P = 1 with A > 32 (1197 = 63 * 19), three-level splits (1540 = 4 * 35 * 11, 1326 = 2 * 39 * 17), the one-buffer
-    variant (536, 640, 520) next to the two-buffer one, and the longest supported row (8192)."""
+    path), P = 1 with A > 32 (1197 = 57 * 21), three-level splits (1540 = 4 * 35 * 11, 1326 = 2 * 39 * 17), the one-buffer
+    variant (536, 640, 520) next to the two-buffer one, and the longest supported row (8192).
+    Small-DFT variant per side: roots-of-unity scalar sums (a factor > 32) for 1072, 536 = 8 * 67, 1197, 1540 and 1326;
+    one-buffer 4 x 2 packed-FMA blocks for 640 = 16 * 8 * 5, 64 = 16 * 2 * 2 and 5; two-buffer MFMA strips for
+    8192 = 16 * 32 * 16 (full 16-row tiles only) and 3024 = 16 * 21 * 9 (A = 21: second tile partial, B = 9: first tile
+    partial; 5 rows: the last row pair is single).  Both sides of (3000, 520) have compiled mixed-radix kernels by now:
+    that shape runs those."""
     from oracle import signal_np as S
 
     rng = np.random.default_rng(shape[0] ^ shape[1])
@@ -481,8 +486,9 @@ def test_fused_transform_factorisations(gs, shape):
 
 @pytest.mark.parametrize("shape", [(1042, 1042), (2056, 2464), (1031, 520), (600, 4093)])
 def test_bluestein_lengths_vs_oracle(gs, shape):
-    """Sides with a large prime factor (1042 = 2 * 521, 2056 = 8 * 257, 1031 and 4093 prime) have no small-factor
-    split: chirp-z over two fused power-of-two transforms.  Same 1e-5 bar."""
+    """Sides with a prime factor beyond the fused split's A + B <= 320 (1042 = 2 * 521, 1031 and 4093 prime) have no
+    small-factor split: chirp-z over two fused power-of-two transforms.  (2056 = 8 * 257 is within the split: fused
+    with A = 257, roots-of-unity variant; that shape checks a general plan away from the other cases' sizes.)  Same 1e-5 bar."""
     from oracle import signal_np as S
 
     rng = np.random.default_rng(shape[0] + 3 * shape[1])

@@ -19,7 +19,11 @@ def pp():
 
 
 @pytest.mark.parametrize("shape,sigma", [((60, 52), 1.5), ((64, 64), (1.0, 2.0)), ((100, 37), 0.7), ((512, 512), 1.5),
-                                         ((70, 258), 0.7), ((258, 258), 0.7),   # 262 = 2 * 131: DFT-matrix fallback
+                                         # padded 262 = 2 * 131 (and 74 = 2 * 37): fused, roots-of-unity small DFTs, pair route
+                                         ((70, 258), 0.7), ((258, 258), 0.7),
+                                         # padded 331 (prime, A + B > 320): DFT-matrix product on x (pad and crop kernels), on y
+                                         # (one-side-fused row passes), on both; 69 x 60: fused pair route with an odd padded height
+                                         ((60, 323), 1.5), ((323, 60), 1.5), ((323, 323), 1.5), ((61, 52), 1.5),
                                          # padded 264 = 8*3*11 / 520 = 8*5*13: the three-kernel mixed-radix route
                                          # (b4d_wiener_mr.hip) on square and both non-square orientations
                                          ((256, 256), 1.5), ((256, 512), 1.5), ((512, 256), 1.5)])
