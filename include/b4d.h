@@ -356,6 +356,41 @@ int b4d_poly2_fit_weighted(const float* w_map, const float* weights, long long w
                            unsigned remove_mask, double scale, int nan_invalid, double* coeff, float* residual, double* rms,
                            void* stream);
 
+/* Modal fits of wavefront maps (barc4dip_amd/signal/modal.py).
+ * Geometry, basis-agnostic: node (i, j) has v = (i - cy) * sy along y and u = (j - cx) * sx along x.
+ *   basis 0, Zernike: modes 1 .. n_modes in Noll's order and normalisation (rms 1 over the unit disc, even j the cosine, theta from
+ *     +x towards +y) in rho = hypot(u, v); the caller passes sy = dy / radius, sx = dx / radius.  Nodes with rho^2 > 1 + 1e-9 have
+ *     weight 0.
+ *   basis 1, Legendre: sqrt(2a+1) sqrt(2b+1) P_a(u) P_b(v), ordered by total degree a + b and within a degree by growing b; the
+ *     caller passes sy = 1 / max(cy, 1), sx = 1 / max(cx, 1).
+ *   The modes are evaluated in float64 by recurrence (no trigonometry, no division by rho); 1 <= n_modes <= 66 (B4D_ESIZE beyond).
+ * b4d_modal_fit: weighted least-squares coefficients of every map.  maps: DEVICE (n, ny, nx) float32.  weights: DEVICE float32,
+ *   (n, ny, nx) with weight_stride = ny * nx, one shared (ny, nx) map with weight_stride = 0, or null for all ones.  A node whose
+ *   weight is not finite and positive, or whose map value is not finite, has weight 0 and its map value enters no sum.  The
+ *   normal equations [A phi]^T W [A phi] are accumulated in float64 on the matrix cores, per chunk of nodes, and the chunks are
+ *   added in a fixed order that depends on (ny, nx, n_modes) alone: a map gives the same bits alone and inside any batch.  They
+ *   are factored by Cholesky without pivoting in mode order; a mode whose remainder after the kept ones is not above 1e-12 of
+ *   its own diagonal entry, or whose diagonal entry is not > 0, is dropped and gets coefficient 0.  coeff: DEVICE (n, n_modes)
+ *   float64; kept: DEVICE (n, n_modes) bytes, 1 for a kept mode.  workspace: DEVICE, b4d_modal_workspace_bytes(n, ny, nx, n_modes)
+ *   bytes (0 for an unsupported shape), 8-byte aligned.
+ * b4d_modal_residual: out = scale * (map - sum of c_j mode_j over the modes with remove[j] != 0; remove: DEVICE n_modes bytes
+ *   shared by the batch, null removes all), evaluated in float64 and stored as float32 (out may be maps itself).
+ *   rms: DEVICE (n) float64, sqrt(sum w r^2 / sum w - (sum w r / sum w)^2) of the stored values over the nodes of positive weight,
+ *   NaN without one.  nan_invalid != 0 writes NaN at the weight-0 nodes, else the subtraction is evaluated there too, outside the
+ *   disc included (a map value that is not finite stays so).  valid: DEVICE (n, ny, nx) bytes or null, 1 at the nodes of positive
+ *   weight.  workspace as for b4d_modal_fit; the rms partials of the workgroups live in it, in a part the fit does not use.
+ * b4d_modal_eval: out (DEVICE (n, ny, nx) float32) = sum of c_j mode_j, coeff DEVICE (n, n_modes) float64; nothing is masked.
+ * Sides 1 .. 2048 (B4D_ESIZE beyond), n <= 65535.  Asynchronous on `stream`; the table of recurrence coefficients is built on
+ * first use (float64 on the host, a blocking upload) and cached per device and basis. */
+size_t b4d_modal_workspace_bytes(int n, int ny, int nx, int n_modes);
+int b4d_modal_fit(const float* maps, const float* weights, long long weight_stride, int n, int ny, int nx, int basis, int n_modes,
+                  double cy, double cx, double sy, double sx, void* workspace, double* coeff, unsigned char* kept, void* stream);
+int b4d_modal_residual(const float* maps, const float* weights, long long weight_stride, int n, int ny, int nx, int basis,
+                       int n_modes, double cy, double cx, double sy, double sx, const double* coeff, const unsigned char* remove,
+                       double scale, int nan_invalid, void* workspace, float* out, double* rms, unsigned char* valid, void* stream);
+int b4d_modal_eval(const double* coeff, int n, int ny, int nx, int basis, int n_modes, double cy, double cx, double sy, double sx,
+                   float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
