@@ -88,6 +88,8 @@ SIGNATURES = {
     "b4d_modal_fit": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "b4d_modal_residual": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp]),
     "b4d_modal_eval": (_i, [_vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp]),
+    "b4d_focal_spot_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "b4d_focal_spot": (_i, [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b4d_uw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

@@ -1,9 +1,10 @@
 """GPU drop-in for ``barc4dip.signal`` (same public names as signal/__init__.py:6-26)."""
 from __future__ import annotations
 
-from . import corr, displacement, fft, modal, tracking, wavefront
+from . import corr, displacement, fft, focus, modal, tracking, wavefront
 from .corr import autocorr2d, autocorr2d_stack, psd_autocorr2d_stack, xcorr2d
 from .displacement import displacement_grid, displacement_map
+from .focus import beam_caustic, focal_spot, focus_geometry
 from .modal import modal_eval, modal_fit, modal_table
 from .tracking import (phase_correlation, phase_correlation_batch, template_matching, template_matching_batch,
                        track_translation)
@@ -18,4 +19,5 @@ __all__ = [
     "displacement", "displacement_map", "displacement_grid",
     "wavefront", "integrate_gradient", "wavefront_from_displacement",
     "modal", "modal_fit", "modal_eval", "modal_table",
+    "focus", "focal_spot", "focus_geometry", "beam_caustic",
 ]

@@ -241,7 +241,8 @@ def wavefront_from_displacement(field, *, pixel_size, distance, wavelength=None,
     (on a centred regular grid the tilt terms of the 6-term fit are the tilt-only fit), ``"quadratic"`` all six, which leaves
     the figure error.
     Returns {"wavefront": metres, shape of ``dy``; "phase": ``2 pi wavefront / wavelength`` (only with a wavelength); "y", "x":
-    the grid axes in pixels; "coefficients": (T, 6) float64 in metres per metre^degree; "radius_x" = 1 / (2 c3), "radius_y"
+    the grid axes in pixels; "remove": the argument, so that a consumer (``focal_spot``) knows what was subtracted;
+    "coefficients": (T, 6) float64 in metres per metre^degree; "radius_x" = 1 / (2 c3), "radius_y"
     = 1 / (2 c5): (T,) float64 metres, inf where the coefficient is 0; "rms": (T,) float64, the standard deviation (ddof 0) of
     the returned wavefront}.  T = 1 for a 2-D field.  Maps are float64 NumPy, or float32 device tensors with
     ``return_tensors=True``.
@@ -264,7 +265,7 @@ def wavefront_from_displacement(field, *, pixel_size, distance, wavelength=None,
     torch = _ffi.require_gpu()
     ny, nx = shape[-2:]
     lib, st = _ffi.lib(), _ffi.stream_ptr()
-    res = {"y": y, "x": x}
+    res = {"y": y, "x": x, "remove": remove}
     # integrated in pixel units (shifts in px on a grid of `step` px), scaled to metres by the last kernel: float32 never sees
     # the physical magnitudes
     if weighted:

@@ -391,6 +391,35 @@ int b4d_modal_residual(const float* maps, const float* weights, long long weight
 int b4d_modal_eval(const double* coeff, int n, int ny, int nx, int basis, int n_modes, double cy, double cx, double sy, double sx,
                    float* out, void* stream);
 
+/* Focal spot and caustic of a measured wavefront (barc4dip_amd/signal/focus.py): the Fresnel integral of
+ * one pupil per (map, plane) pair as a zero-padded 2-D DFT on the canvas (Py, Px) of a plan from b4d_plan_create_general.
+ * Node (i, j) of map t has v = (i - (ny-1)/2) hy along y and u = (j - (nx-1)/2) hx along x (metres) and the phase, in float64,
+ *   phi = (2 pi / wavelength) (err + c0 + c1 u + c2 v + c3 u^2 + c4 u v + c5 v^2) + (pi / (wavelength z)) (u^2 + v^2),
+ * c = coeff[t], z = z[k] the signed distance of plane k from the measurement plane.  The pupil A exp(i phi) -- A = amp, or 1
+ * without one -- sits at [0:ny, 0:nx] of the zero canvas; a node whose err is not finite, or whose amp is not finite and > 0,
+ * is outside the aperture (pupil 0, no part in any sum).  The plane's intensity is I = |fftshift(fft2(canvas))|^2 / (sum A)^2,
+ * sum A over the valid nodes of the map in float64: the unit is the peak of the aberration-free, in-focus pupil of the same
+ * amplitude, so the peak of I is the Strehl ratio, and sum I = Py Px sum A^2 / (sum A)^2.
+ *   err: DEVICE (n, ny, nx) float32, metres.  amp: DEVICE float32 or NULL; (n, ny, nx) with amp_stride = ny * nx, or one map
+ *   shared by all with amp_stride = 0.  coeff: DEVICE (n, 6) float64.  z: HOST (nz) float64, each finite and non-zero (read
+ *   before the call returns).  ny <= Py, nx <= Px; Py, Px <= 4096.
+ *   intensity: NULL, or DEVICE (n, nz, cy, cx) float32: the window of cy x cx bins centred on the DC bin, rows
+ *   Py/2 - cy/2 .. Py/2 - cy/2 + cy - 1 of the shifted plane and likewise along x; cy <= Py, cx <= Px.
+ *   stats: DEVICE (n, nz, 10) float64 over the WHOLE canvas, p and q the integer bin offsets from the DC bin along y and x:
+ *     [0] sum I   [1] peak of I   [2] first index of the peak in row-major order of the shifted plane (row * Px + column)
+ *     [3] sum I p   [4] sum I q   [5] sum I p^2   [6] sum I q^2   [7] sum I p q   [8] sum A   [9] sum A^2
+ *   marg_x: NULL or DEVICE (n, nz, Px) float64, the sum of I over the rows; marg_y: NULL or DEVICE (n, nz, Py), over the columns;
+ *   both in shifted order.  A map without a valid node gets NaN in [0] .. [7], in its marginals and in its intensity, no error.
+ *   workspace: DEVICE, b4d_focal_spot_workspace_bytes(plan, n, nz) bytes (0 for a plan or counts that cannot run), 256-byte
+ *   aligned.  The pairs pass through the plan's buffers `chunk` at a time; every sum is taken in an order fixed by (Py, Px), so
+ *   the results are the same bits from run to run and for any chunk.  Asynchronous on `stream`.
+ * B4D_EINVAL: a plan that is not general, a map larger than the canvas, a crop larger than the canvas, nz < 1, a z that is 0 or
+ * not finite, a wavelength or spacing that is not finite and positive. */
+size_t b4d_focal_spot_workspace_bytes(const b4d_plan* plan, int n, int nz);
+int b4d_focal_spot(b4d_plan* general_plan, const float* err, const float* amp, long long amp_stride, int n, int ny, int nx,
+                   const double* coeff, double hy, double hx, double wavelength, const double* z, int nz, int cy, int cx,
+                   float* intensity, double* stats, double* marg_x, double* marg_y, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
