@@ -68,6 +68,9 @@ namespace b4d {
 
 constexpr int E16 = 16;
 
+typedef float f32x2 __attribute__((ext_vector_type(2)));   // plain vector values for accesses through address-space pointers
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 // radix plans: N = 16 * R2 * R3 with 16 points per lane
 constexpr int radix2(int n) { return n / 16 < 16 ? n / 16 : 16; }
 constexpr int radix3(int n) { return n / (16 * radix2(n)); }
@@ -126,7 +129,12 @@ struct RowSrc {
 // YS ("ysplit" route, ny = 2048): transform p packs rows p and p + ny/2 and applies the first radix-2 stage of the COLUMN
 // transform to their half spectra A, B: A + B -> row p of the even-ky tile set, (A - B) w^p -> row p of the odd one
 // (w^p = tw_y[p], uniform per transform).  Layout [frame][parity][ct][p][c], ct_w columns per tile.
-template <int NX, int SEQ, bool SRC, int ITER = 1, bool YS = false>
+// W16 (YS only; "row16" of b4d_set_option): 16-byte stores.  The Hermitian split reads every bin from the exchange buffer, so the
+// lane that stores a bin need not be the lane that transformed it: lane u splits bins k, k + 1, k = 2(u + T j), j < 4, and stores
+// 16 bytes into the even and into the odd tile row (8 instead of 16 stores per lane, whole lines per wave instruction).  Same
+// expressions, same values bit for bit; needs a 16-byte-aligned workspace (launch_r2c).  The loads stay one dword per lane: 16-byte
+// loads, redistributed through the buffer or by quad transposes, were measured and dropped.
+template <int NX, int SEQ, bool SRC, int ITER = 1, bool YS = false, bool W16 = false>
 __global__ void __launch_bounds__((NX / E16) * SEQ)
 k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __restrict__ nyq_rows,
           const float2* __restrict__ tw, int ny, int ct_w, const RowSrc* __restrict__ srcs, const float2* __restrict__ tw_y) {
@@ -135,7 +143,9 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
     constexpr bool WV = T <= 64;   // one transform = (part of) one wavefront: no workgroup barriers (fft_sync)
     static_assert(ITER == 1 || !SRC, "ROI sources run one group per workgroup");
     static_assert(!YS || !SRC, "the ysplit pairing takes full frames");
-    __shared__ float2 lds_all[SEQ * G::LDS_ELEMS];
+    static_assert(!W16 || YS, "16-byte stores: parity-tile route only");
+    static_assert(!W16 || G::LDS_ELEMS % 2 == 0, "16-byte accesses to each transform's buffer");
+    __shared__ __attribute__((aligned(16))) float2 lds_all[SEQ * G::LDS_ELEMS];
     const int seq = threadIdx.x / T, u = threadIdx.x % T;
     const size_t frame = blockIdx.y;
     if (SRC) {   // rows outside the ROI are zero: a workgroup without a ROI row writes NOTHING -- the column pass and k_nyq
@@ -187,7 +197,38 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
 #pragma unroll
         for (int j = 0; j < E; ++j) lds[u + T * j] = v[j];
         fft_sync<WV>();
-        if (live) {
+        if (W16) {
+            if (live) {
+                const float2 wp = tw_y[pair];
+                const f32x4* l4 = reinterpret_cast<const f32x4*>(lds);
+#pragma unroll
+                for (int j = 0; j < E / 4; ++j) {
+                    const int k = 2 * (u + T * j);
+                    const f32x4 zz = l4[u + T * j];   // bins k, k + 1
+                    const float2 z2[2] = {make_float2(zz.x, zz.y), make_float2(zz.z, zz.w)};
+                    const float2 zr2[2] = {lds[(NX - k) & (NX - 1)], lds[NX - k - 1]};
+                    float2 ev[2], od[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const float2 z = z2[h], zr = zr2[h];
+                        float2 a = make_float2(0.5f * (z.x + zr.x), 0.5f * (z.y - zr.y));
+                        float2 b = make_float2(0.5f * (z.y + zr.y), 0.5f * (zr.x - z.x));
+                        if (h == 0 && k == 0) {  // DC bins are real; the (real) Nyquist bins of both rows go to the side array
+                            const float2 zn = lds[NX / 2];
+                            a = make_float2(z.x, 0.f);
+                            b = make_float2(z.y, 0.f);
+                            nyq_rows[frame * ny + pair] = zn.x;
+                            nyq_rows[frame * ny + pair + ny / 2] = zn.y;
+                        }
+                        ev[h] = cadd(a, b);
+                        od[h] = cmul(csub(a, b), wp);
+                    }
+                    const size_t o = spec_index(2 * frame, nt, ny / 2, ct_w, pair, k);
+                    *reinterpret_cast<f32x4*>(spec + o) = f32x4{ev[0].x, ev[0].y, ev[1].x, ev[1].y};
+                    *reinterpret_cast<f32x4*>(spec + o + (size_t)(ny / 2) * (NX / 2)) = f32x4{od[0].x, od[0].y, od[1].x, od[1].y};
+                }
+            }
+        } else if (live) {
             float2 wp = make_float2(1.f, 0.f);
             if (YS) wp = tw_y[pair];
 #pragma unroll
@@ -279,8 +320,6 @@ struct ColCfg {
     static constexpr size_t LDS_BYTES = sizeof(float2) * (size_t)G::LDS_ELEMS * CPT;   // one exchange region (132 KiB at NY = 2048)
 };
 
-typedef float f32x2 __attribute__((ext_vector_type(2)));   // plain vector values for accesses through address-space pointers
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define B4D_GLOBAL __attribute__((address_space(1)))
 // Address = uniform base + 32-bit BYTE offset of the lane: the form global_load/store take with the base in SGPRs and ONE offset
 // VGPR.  With element indices the compiler cannot fold the scaling into a 32-bit offset (it could wrap) and builds 64-bit
@@ -595,13 +634,23 @@ enum RowOutMode { C2R_OUT = 0, C2R_PEAK = 1, C2R_MAG = 2, C2R_ROWS = 3 };
 // of the power columns, rows 0 .. h/2 of each parity tile, h = ny/2.  Transform y combines row y of both:
 // t = conj(w^y) O, G(y) = E + t, G(h - y) = conj(E - t), and packs THESE two rows; rows y, h - y and their point mirrors
 // -y, h + y are written, every row of the map once.
-template <int NX, int SEQ, int MODE, int UNIT = 0, bool YS = false>
+// W16 (YS, C2R_OUT; "row16" of b4d_set_option): 16 bytes per lane in every global access, whole lines per wave instruction, the same
+// values bit for bit; needs 16-byte-aligned workspace and output (launch_c2r).  The exchange buffer is free before stage 1 and
+// after stage 3, so the lane that moves an element need not be the lane that transforms it:
+//   loads   lane u loads bins k, k + 1, k = 2(u + T j), j < 4, of the E and O tile rows (8 instead of 16 loads), writes both
+//           Hermitian halves to the buffer and reads all 16 registers back
+//   stores  the scaled rows go through the buffer as pairs (row b, row a) at x; lane u stores output columns 4u + 4T i ... + 3 of the
+//           two direct rows (x ascending from an aligned start) and of the two mirror rows (x = nx/2 - c descending: one 16-byte
+//           and two 8-byte LDS reads) -- 16 instead of 64 stores
+template <int NX, int SEQ, int MODE, int UNIT = 0, bool YS = false, bool W16 = false>
 __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
     static_assert(!YS || MODE == C2R_OUT || MODE == C2R_PEAK, "ysplit: autocorrelation output only");
+    static_assert(!W16 || (YS && MODE == C2R_OUT), "16-byte accesses: parity-tile autocorrelation output only");
     using G = RowGeom<NX>;
     constexpr int T = G::T, E = E16;
     constexpr bool WV = T <= 64;   // the transform's own exchanges are wave-local; the reductions ACROSS transforms below keep s_barrier
-    __shared__ float2 lds_all[SEQ * G::LDS_ELEMS];
+    static_assert(!W16 || G::LDS_ELEMS % 2 == 0, "16-byte accesses to each transform's buffer");
+    __shared__ __attribute__((aligned(16))) float2 lds_all[SEQ * G::LDS_ELEMS];
     const int seq = threadIdx.x / T, u = threadIdx.x % T;
     const size_t frame = blockIdx.y;
     const int ny = p.ny, ct_w = p.ct_w, nt = (NX / 2) / ct_w;
@@ -645,6 +694,28 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
         wc = p.tw_y[yl];
         wc.y = -wc.y;
     }
+    if (W16) {
+#pragma unroll
+        for (int j = 0; j < E / 4; ++j) {
+            const int k = 2 * (u + T * j);
+            const size_t o = spec_index(2 * frame, nt, ny / 2, ct_w, yl, k);
+            const f32x4 e4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.g + o)),
+                        o4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(p.g + o + (size_t)(ny / 2) * (NX / 2)));
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const float2 ev = h ? make_float2(e4.z, e4.w) : make_float2(e4.x, e4.y);
+                const float2 t = cmul(h ? make_float2(o4.z, o4.w) : make_float2(o4.x, o4.y), wc);
+                const float2 a = cadd(ev, t), d = csub(ev, t), b = make_float2(d.x, -d.y);
+                if (h == 0 && k == 0) {  // DC and Nyquist bins of both rows are real
+                    lds[0] = make_float2(b.x, a.x);
+                    lds[NX / 2] = make_float2(p.gnyq[frame * ny + ny / 2 - yl], p.gnyq[frame * ny + yl]);
+                } else {
+                    lds[k + h] = make_float2(a.y + b.x, a.x - b.y);        // swap(A + iB)
+                    lds[NX - k - h] = make_float2(b.x - a.y, a.x + b.y);  // swap(conj A + i conj B)
+                }
+            }
+        }
+    } else
 #pragma unroll
     for (int j = 0; j < E / 2; ++j) {
         const int k = u + T * j;
@@ -681,7 +752,7 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
     }
     fft_sync<WV>();
 #pragma unroll
-    for (int j = E / 2; j < E; ++j) v[j] = lds[u + T * j];
+    for (int j = W16 ? 0 : E / 2; j < E; ++j) v[j] = lds[u + T * j];
     fft_sync<WV>();
     Fft3<G, 1, WV>::run(v, v, u, 0, lds, p.tw);
     // v[j] = swap(z[x]), x = u + T j: row 2*pair = Re z = v.y, row 2*pair+1 = Im z = v.x
@@ -695,7 +766,7 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
     float* o0 = p.out + (frame * ny + ra) * (size_t)NX;
     float* o1 = p.out + (frame * ny + rb) * (size_t)NX;
     if (MODE == C2R_OUT) {
-        if (!live) return;
+        if (!W16 && !live) return;   // W16: idle transforms leave behind the barriers of the redistribution
         const bool norm = (p.flags & B4D_NORM_PEAK) != 0;
         float s = p.scale;
         bool unit_peak = false;   // corr / max|corr| only if the peak is > 0 (signal/corr.py:247-250): a constant frame stays 0
@@ -710,6 +781,35 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
         const bool mir0 = YS ? y0 >= 1 : p.half && y0 >= 1 && y0 < ny / 2, mir1 = YS ? y0 >= 1 && 4 * y0 < ny : p.half && y0 + 1 < ny / 2;
         float* q0 = p.out + (frame * ny + ((ny / 2 - y0) & (ny - 1))) * (size_t)NX;
         float* q1 = p.out + (frame * ny + ((ny / 2 - y1) & (ny - 1))) * (size_t)NX;
+        if (W16) {
+            fft_sync<WV>();   // the transform's last exchange has been read
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                const int x = u + T * j;
+                float r0 = v[j].y * s;
+                const float r1 = v[j].x * s;
+                if (unit_peak && pair == 0 && x == 0) r0 = 1.0f;  // peak normalisation: zero lag is 1 by definition
+                lds[x] = make_float2(r1, r0);
+            }
+            fft_sync<WV>();
+            if (!live) return;
+            const f32x4* l4 = reinterpret_cast<const f32x4*>(lds);
+#pragma unroll
+            for (int i = 0; i < E / 4; ++i) {
+                const int c = 4 * u + 4 * T * i, x = (c + NX / 2) & (NX - 1);   // columns c ... c + 3 hold x ... x + 3
+                const f32x4 d0 = l4[x / 2], d1 = l4[x / 2 + 1];
+                __builtin_nontemporal_store(f32x4{d0.y, d0.w, d1.y, d1.w}, reinterpret_cast<f32x4*>(o0 + c));
+                if (wr1) __builtin_nontemporal_store(f32x4{d0.x, d0.z, d1.x, d1.z}, reinterpret_cast<f32x4*>(o1 + c));
+                if (mir0 || mir1) {   // columns c ... c + 3 of a mirror row hold xs, xs - 1, xs - 2, xs - 3 (mod NX)
+                    const int xs = (NX / 2 - c) & (NX - 1);
+                    const float2 m0 = lds[xs], m3 = lds[(xs - 3) & (NX - 1)];
+                    const f32x4 m12 = l4[((xs - 2) & (NX - 1)) / 2];
+                    if (mir0) __builtin_nontemporal_store(f32x4{m0.y, m12.w, m12.y, m3.y}, reinterpret_cast<f32x4*>(q0 + c));
+                    if (mir1) __builtin_nontemporal_store(f32x4{m0.x, m12.z, m12.x, m3.x}, reinterpret_cast<f32x4*>(q1 + c));
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < E; ++j) {
             const int x = u + T * j, c = (x + NX / 2) & (NX - 1), cm = (NX / 2 - x) & (NX - 1);
@@ -962,7 +1062,9 @@ struct Route {
     bool parity;           // "ysplit" route of 2048-row frames: parity tiles of ny/2 rows; otherwise tiles of all ny rows
     int ct_w;              // complex columns per tile
     const float2* tw_col;  // twiddles of the transform the column pass runs: ny/2 points on parity tiles, ny points otherwise
+    int row16;             // parity route: the row passes may move 16 bytes per lane ("row16"); their launchers check the alignment
 };
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // Launchers: one per pass, the route (YS: parity tiles) a template argument.  A dispatcher instantiates every kernel it names in the
 // including unit: the plain-route ones (dispatch_r2c, dispatch_c2r) are ordinary functions, the *_route templates let the one unit
@@ -1015,16 +1117,21 @@ static int dispatch_nyq(const b4d_plan* pl, NyqArgs a, int items, hipStream_t st
 // YS: rows p and p + ny/2 per transform, parity tile sets (full frames only); otherwise srcs != null selects ROI / z-score sources
 template <int NX, bool YS>
 static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, const RowSrc* srcs, int ct_w, int batch,
-                      hipStream_t st) {
+                      hipStream_t st, int row16) {
     constexpr int SEQ = row_seq(NX);
     constexpr int ITER = NX >= 1024 ? B4D_K1_ITER : 1;   // groups of row pairs per workgroup, full frames only
     const dim3 block((NX / E16) * SEQ), grid((pl->ny / 2 + SEQ - 1) / SEQ, batch),
         grid_full((pl->ny / 2 + SEQ * ITER - 1) / (SEQ * ITER), batch);
     if (YS && srcs) return fail(B4D_EINVAL, "parity tiles take full frames");
-    if constexpr (YS)
-        hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, srcs,
-                           pl->tw_y);
-    else if (srcs)
+    if constexpr (YS) {
+        // 16-byte stores need a 16-byte-aligned workspace (the loads are dwords: the frames may sit anywhere); the narrow kernel otherwise
+        if (row16 && aligned16(spec))
+            hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny,
+                               ct_w, srcs, pl->tw_y);
+        else
+            hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w,
+                               srcs, pl->tw_y);
+    } else if (srcs)
         hipLaunchKernelGGL((k_row_r2c<NX, SEQ, true>), grid, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny, ct_w, srcs,
                            (const float2*)nullptr);
     else
@@ -1035,8 +1142,8 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
 }
 template <bool YS>
 static int dispatch_r2c_route(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows,
-                              const RowSrc* srcs, int ct_w) {
-#define B4D_CALL(N) launch_r2c<N, YS>(pl, in, spec, nyq_rows, srcs, ct_w, batch, st)
+                              const RowSrc* srcs, int ct_w, int row16 = 0) {
+#define B4D_CALL(N) launch_r2c<N, YS>(pl, in, spec, nyq_rows, srcs, ct_w, batch, st, row16)
     B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported nx");
@@ -1054,7 +1161,7 @@ static int dispatch_r2c(const b4d_plan* pl, const float* in, int batch, hipStrea
 // YS: C2R_OUT on the parity tiles (a.ct_w, a.tw_y), always the half form.
 template <int NX, bool YS>
 static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mode, hipStream_t st,
-                      std::vector<hipEvent_t>* ev, int* nblk) {
+                      std::vector<hipEvent_t>* ev, int* nblk, int row16) {
     constexpr int SEQ = row_seq(NX);
     const int npairs = (YS || (a.half && mode == C2R_OUT)) ? pl->ny / 4 + 1 : pl->ny / 2;
     const dim3 grid((npairs + SEQ - 1) / SEQ, batch), block((NX / E16) * SEQ);
@@ -1087,14 +1194,22 @@ static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mo
             B4D_HIP(hipEventRecord(e, st));
         }
     }
-    hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS>), grid, block, 0, st, a);
+    if constexpr (YS) {
+        // 16-byte accesses need 16-byte-aligned output (the C ABI does not promise it) and workspace: the narrow kernel otherwise
+        if (row16 && aligned16(a.g) && aligned16(a.out))
+            hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS, true>), grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS>), grid, block, 0, st, a);
+    } else {
+        hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS>), grid, block, 0, st, a);
+    }
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
 template <bool YS>
 static int dispatch_c2r_route(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, int mode, std::vector<hipEvent_t>* ev,
-                              int* nblk) {
-#define B4D_CALL(N) launch_c2r<N, YS>(pl, a, batch, mode, st, ev, nblk)
+                              int* nblk, int row16 = 0) {
+#define B4D_CALL(N) launch_c2r<N, YS>(pl, a, batch, mode, st, ev, nblk, row16)
     B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported nx");

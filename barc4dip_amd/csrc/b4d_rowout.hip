@@ -6,6 +6,6 @@
 
 namespace b4d {
 int row_out_pass(const b4d_plan* pl, const RowOutArgs& a, int batch, hipStream_t st, std::vector<hipEvent_t>* ev, const Route& rt) {
-    return rt.parity ? dispatch_c2r_route<true>(pl, a, batch, st, C2R_OUT, ev, nullptr) : dispatch_c2r(pl, a, batch, st, C2R_OUT, ev);
+    return rt.parity ? dispatch_c2r_route<true>(pl, a, batch, st, C2R_OUT, ev, nullptr, rt.row16) : dispatch_c2r(pl, a, batch, st, C2R_OUT, ev);
 }
 }  // namespace b4d

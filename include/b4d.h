@@ -58,6 +58,11 @@ const char* b4d_last_error(void);
  *                        every second spectrum row and stores whole 128-byte PSD lines; 0 = 16-column tiles of all rows.  The
  *                        route depends on the frame shape alone (results of a stack equal those of its frames, bit for bit); the
  *                        two routes split the column transform differently and agree to float32 rounding, not bit for bit.
+ *   "row16"              0 / 1 (default 1): 1 = on the "ysplit" route the row passes move 16 bytes per lane to and from device memory
+ *                        (the inverse row pass all of its loads and stores, the forward row pass its stores) where the pointers
+ *                        allow it: the workspace, and for the inverse pass the caller's `autocorr`, must be 16-byte aligned --
+ *                        checked per call, the 4- and 8-byte kernels run otherwise; 0 = the 4- and 8-byte kernels always.  Only
+ *                        which lane moves which element differs: results are bit-identical.
  *   "exp"                0 .. 255 (default 0): development switch for A/B runs of kernel variants under test in ONE process
  *                        (tools/dev_*.py); a shipped library has no reader of it.
  * Values outside an option's range and unknown names return B4D_EINVAL; the options are atomics, read once per entry-point call. */
