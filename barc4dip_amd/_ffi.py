@@ -90,7 +90,13 @@ SIGNATURES = {
     "b4d_modal_eval": (_i, [_vp, _i, _i, _i, _i, _i, _d, _d, _d, _d, _vp, _vp]),
     "b4d_focal_spot_workspace_bytes": (_sz, [_vp, _i, _i]),
     "b4d_focal_spot": (_i, [_vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp, _d, _d, _d, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "b4d_uw_step": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
+    "b4d_fringe_demodulate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "b4d_fringe_demodulate": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "b4d_fringe_compare": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b4d_phase_unwrap_workspace_bytes": (_sz, [_i, _i, _i]),
+    "b4d_phase_unwrap": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "b4d_fringe_shift": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 
 

@@ -762,9 +762,68 @@ static void wf_poisson(const WfBasis* by, const WfBasis* bx, const float* rhs, f
     hipLaunchKernelGGL(k_wf_gemm<false>, grid, dim3(256), 0, st, p4);
 }
 
+// ---- phase unwrapping: the wrapped differences of neighbouring nodes are the EDGE slopes of the same
+// 5-point Neumann problem (no Southwell means), so the right-hand side is their divergence and wf_poisson solves it; the
+// congruence step then moves every node by the whole number of turns that brings it closest to the solution.
+__device__ __forceinline__ float wf_wrap(float a) { return a - 6.283185307179586f * rintf(a * 0.15915494309189535f); }
+
+// r[i][j] = W(ph[i][j] - ph[i-1][j]) - W(ph[i+1][j] - ph[i][j]) + W(ph[i][j] - ph[i][j-1]) - W(ph[i][j+1] - ph[i][j]), terms with
+// a node outside the grid absent.  grid (ceil(ny nx / 256), batch)
+__global__ void __launch_bounds__(256) k_wf_unwrap_rhs(const float* __restrict__ ph, int ny, int nx, float* __restrict__ r) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ny * nx) return;
+    const size_t fo = (size_t)blockIdx.y * ny * nx;
+    const int i = e / nx, j = e % nx;
+    const float* __restrict__ p = ph + fo + e;
+    const float c = p[0];
+    float s = 0.f;
+    if (i > 0) s += wf_wrap(c - p[-nx]);
+    if (i + 1 < ny) s -= wf_wrap(p[nx] - c);
+    if (j > 0) s += wf_wrap(c - p[-1]);
+    if (j + 1 < nx) s -= wf_wrap(p[1] - c);
+    r[fo + e] = s;
+}
+
+// out = ph + 2 pi round((p + (ph[c] - p[c]) - ph) / 2 pi) with c the node (ny / 2, nx / 2); a node that keeps its level keeps its bits
+__global__ void __launch_bounds__(256) k_wf_unwrap_congruence(const float* __restrict__ ph, const float* __restrict__ p, int ny, int nx,
+                                                              float* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= ny * nx) return;
+    const size_t fo = (size_t)blockIdx.y * ny * nx;
+    const size_t c = fo + (size_t)(ny / 2) * nx + nx / 2;
+    const float shift = ph[c] - p[c];
+    const float v = ph[fo + e];
+    const float k = rintf((p[fo + e] + shift - v) * 0.15915494309189535f);
+    out[fo + e] = k == 0.f ? v : (float)((double)v + 6.283185307179586 * (double)k);
+}
+
 }  // namespace b4d
 
 using namespace b4d;
+
+extern "C" size_t b4d_phase_unwrap_workspace_bytes(int n, int ny, int nx) {
+    if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
+    return 2 * wf_align256((size_t)n * ny * nx * sizeof(float));
+}
+
+extern "C" int b4d_phase_unwrap(const float* phase, int n, int ny, int nx, void* workspace, float* out, void* stream) {
+    if (!phase || !workspace || !out) return fail(B4D_EINVAL, "null argument");
+    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    const long long plane = (long long)ny * nx;
+    float* p = (float*)workspace;
+    float* scratch = (float*)((char*)workspace + wf_align256((size_t)n * plane * sizeof(float)));
+    std::lock_guard<std::mutex> lk(wf_mutex());     // basis pointers stay valid until the launches below are queued
+    const WfBasis *by = nullptr, *bx = nullptr;
+    if (const int rc = wf_basis(ny, ny, &by)) return rc;
+    if (const int rc = wf_basis(nx, ny, &bx)) return rc;
+    const dim3 grid((unsigned)((plane + 255) / 256), n);
+    hipLaunchKernelGGL(k_wf_unwrap_rhs, grid, dim3(256), 0, st, phase, ny, nx, p);
+    wf_poisson(by, bx, p, scratch, p, n, ny, nx, 1.0, 1.0, nullptr, st);
+    hipLaunchKernelGGL(k_wf_unwrap_congruence, grid, dim3(256), 0, st, phase, (const float*)p, ny, nx, out);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
 
 extern "C" size_t b4d_integrate_workspace_bytes(int n, int ny, int nx) {
     if (n < 1 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;

@@ -1,10 +1,11 @@
 """GPU drop-in for ``barc4dip.signal`` (same public names as signal/__init__.py:6-26)."""
 from __future__ import annotations
 
-from . import corr, displacement, fft, focus, modal, tracking, wavefront
+from . import corr, displacement, fft, focus, fringes, modal, tracking, wavefront
 from .corr import autocorr2d, autocorr2d_stack, psd_autocorr2d_stack, xcorr2d
 from .displacement import displacement_grid, displacement_map
 from .focus import beam_caustic, focal_spot, focus_geometry
+from .fringes import (coarse_carriers, fringe_carriers, fringe_demodulate, fringe_displacement, fringe_grid, phase_unwrap)
 from .modal import modal_eval, modal_fit, modal_table
 from .tracking import (phase_correlation, phase_correlation_batch, template_matching, template_matching_batch,
                        track_translation)
@@ -20,4 +21,5 @@ __all__ = [
     "wavefront", "integrate_gradient", "wavefront_from_displacement",
     "modal", "modal_fit", "modal_eval", "modal_table",
     "focus", "focal_spot", "focus_geometry", "beam_caustic",
+    "fringes", "fringe_grid", "fringe_demodulate", "phase_unwrap", "coarse_carriers", "fringe_carriers", "fringe_displacement",
 ]

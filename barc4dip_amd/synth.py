@@ -149,3 +149,23 @@ def degenerate_tracking_inputs(shape, tpl_hw, *, seed: int):
         "whole_frame": (base, np.roll(base, (3, -2), axis=(0, 1)), (0, H, 0, W)),
         "one_row": (base, frame, edge_roi(shape, (1, 31))),
     }
+
+
+def fringe_frame(shape, carriers, displacement=None, *, visibility=0.4, envelope=None, mean: float = 1.0, seed=None) -> np.ndarray:
+    """Grating interferogram (H, W) float64: ``mean * envelope(y, x) * (1 + sum_k visibility_k cos(2 pi f_k . (r - u(r))))``.
+
+    ``carriers``: (K, 2) rows (fy, fx) in cycles per pixel; ``visibility``: a number or one per carrier; ``displacement`` and
+    ``envelope``: callables of the pixel coordinate arrays ``(y, x)`` ((H, 1) and (1, W)) returning ``(uy, ux)`` and the envelope
+    (``None``: no displacement, envelope 1).  With ``seed`` the frame is Poisson noise of that intensity, ``mean`` in counts."""
+    H, W = (int(s) for s in shape)
+    f = np.atleast_2d(np.asarray(carriers, dtype=np.float64))
+    vis = np.broadcast_to(np.asarray(visibility, dtype=np.float64), (f.shape[0],))
+    y, x = np.arange(H, dtype=np.float64)[:, None], np.arange(W, dtype=np.float64)[None, :]
+    uy, ux = (0.0, 0.0) if displacement is None else displacement(y, x)
+    frame = np.ones((H, W))
+    for (fy, fx), v in zip(f, vis):
+        frame = frame + v * np.cos(2.0 * np.pi * (fy * (y - uy) + fx * (x - ux)))
+    frame *= mean * (1.0 if envelope is None else envelope(y, x))
+    if seed is not None:
+        frame = np.random.default_rng(seed).poisson(frame).astype(np.float64)
+    return frame

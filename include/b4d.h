@@ -425,6 +425,46 @@ int b4d_focal_spot(b4d_plan* general_plan, const float* err, const float* amp, l
                    const double* coeff, double hy, double hx, double wavelength, const double* z, int nz, int cy, int cx,
                    float* intensity, double* stats, double* marg_x, double* marg_y, void* workspace, void* stream);
 
+/* Fringe analysis of grating interferograms (barc4dip_amd/signal/fringes.py).
+ * Window grid: origins y0 = Y sty for every Y with y0 + wy <= H (gy of them), likewise x0 = X stx (gx); no search margin.
+ * Taper: the half-sample Hann h_w[j] = 0.5 - 0.5 cos(2 pi (j + 0.5) / w), j = 0 .. w-1.
+ * b4d_fringe_demodulate: for every frame and carrier f_k = (fy, fx) = carriers[2k], carriers[2k+1] (HOST float64, cycles per
+ *   pixel, read before the call returns) the harmonic map
+ *     S_k[Y][X] = sum_j sum_i h_wy[j] h_wx[i] I[y0+j][x0+i] exp(-2 pi i (fy (y0+j) + fx (x0+i))) / (sum h_wy . sum h_wx)
+ *   with ABSOLUTE pixel coordinates in the phase, whose argument is reduced modulo 1 in float64 before it is rounded to float32.
+ *   frames: DEVICE (n, H, W) float32.  out: DEVICE (n, n_carriers + 1, gy, gx) complex64; plane 0 is S_0, the same sum with
+ *   f = 0 (imaginary part 0), plane k + 1 is S_k.  1 <= n_carriers <= 4; windows 2 .. 256 px per axis (B4D_ESIZE beyond), steps
+ *   >= 1, n <= 65535.  float32 sums in an order fixed by the geometry: a frame gives the same bits alone and inside any batch.
+ *   workspace: DEVICE, b4d_fringe_demodulate_workspace_bytes(n_carriers, H, W, wy, wx) bytes (0 for unsupported arguments),
+ *   256-byte aligned: the taper and phasor tables, written by the call.
+ * b4d_fringe_compare: elementwise on harmonic maps.  sample: DEVICE (n, n_carriers + 1, gy, gx) complex64.  reference: the same
+ *   with reference_stride = (n_carriers + 1) gy gx (one per sample), one set shared by all with reference_stride = 0, or NULL
+ *   (absolute mode).  Per node and carrier k:
+ *     phase[k] = arg(S_k conj R_k) in (-pi, pi] (arg S_k in absolute mode)      visibility[k] = 2 |S_k| / S_0
+ *     transmission = S_0 / R_0      dark_field[k] = (|S_k| / S_0) / (|R_k| / R_0)      peak = min_k visibility[k]
+ *   phase, visibility, dark_field: DEVICE (n, n_carriers, gy, gx) float32; transmission: DEVICE (n, gy, gx) float32; peak: DEVICE
+ *   (n, gy, gx) float64.  transmission and dark_field are required with a reference and not written without one.
+ * b4d_phase_unwrap: least-squares unwrapping with a congruence step, per map.  The wrapped differences W(a) = a - 2 pi round(a / 2 pi)
+ *   of neighbouring nodes along y and x are the edge slopes of the 5-point Neumann Poisson problem of b4d_integrate_gradient
+ *   (unit spacings, no Southwell means); its zero-mean solution p, shifted to equal the input at node (ny / 2, nx / 2), selects
+ *   the level: out = phase + 2 pi round((p - phase) / 2 pi).  The data are never smoothed, and a node whose level is 0 keeps its
+ *   bits.  Whole-grid and unweighted: a node that is not finite spoils its map.  phase, out: DEVICE (n, ny, nx) float32, distinct;
+ *   workspace: DEVICE, b4d_phase_unwrap_workspace_bytes(n, ny, nx) bytes (0 for an unsupported shape).  Sides 1 .. 2048
+ *   (B4D_ESIZE beyond), n <= 65535.
+ * b4d_fringe_shift: (dy, dx) = -Minv (phase1, phase2) / 2 pi per node, in float64.  minv: HOST 4 float64, row-major inverse of
+ *   M = [[f1y, f1x], [f2y, f2x]].  phase1, phase2: DEVICE float32, map m at offset m * stride (stride >= gy gx); dy, dx: DEVICE
+ *   (n, gy, gx) float64.
+ * All four are asynchronous on `stream` and have no host fallback. */
+size_t b4d_fringe_demodulate_workspace_bytes(int n_carriers, int H, int W, int wy, int wx);
+int b4d_fringe_demodulate(const float* frames, int n, int H, int W, const double* carriers, int n_carriers, int wy, int wx, int sty,
+                          int stx, void* workspace, void* out, void* stream);
+int b4d_fringe_compare(const void* sample, const void* reference, long long reference_stride, int n, int n_carriers, int gy, int gx,
+                       float* phase, float* visibility, float* transmission, float* dark_field, double* peak, void* stream);
+size_t b4d_phase_unwrap_workspace_bytes(int n, int ny, int nx);
+int b4d_phase_unwrap(const float* phase, int n, int ny, int nx, void* workspace, float* out, void* stream);
+int b4d_fringe_shift(const float* phase1, const float* phase2, long long stride, int n, int gy, int gx, const double* minv, double* dy,
+                     double* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
