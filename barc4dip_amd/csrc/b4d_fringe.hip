@@ -1,5 +1,6 @@
 // b4d_fringe.hip -- fringe analysis of grating interferograms: windowed Fourier demodulation of frames
-// at a few carriers, the elementwise comparison of sample and reference harmonics, and the phase -> displacement map.
+// at a few carriers, the elementwise comparison of sample and reference harmonics, the phase -> displacement map, and the node
+// weights of the weighted unwrap.
 //
 // Harmonic map of carrier f = (fy, fx) on the window grid (origins y0 = Y sty, x0 = X stx, half-sample Hann taper h):
 //   S_f[Y][X] = sum_j sum_i h_wy[j] h_wx[i] I[y0+j][x0+i] exp(-2 pi i (fy (y0+j) + fx (x0+i))) / (sum h_wy . sum h_wx)
@@ -225,6 +226,110 @@ __global__ void __launch_bounds__(256) k_fr_shift(const float* __restrict__ p1, 
     dx[m * plane + e] = -(m10 * a + m11 * b) * (0.5 * M_1_PI);
 }
 
+// ---- node weights for the weighted unwrap.  A node is valid if S_0 >= min_level max(S_0 of its frame),
+// the same for R_0 where there is a reference, and every visibility 2 |S_k| / S_0 (and 2 |R_k| / R_0) >= min_visibility; a
+// threshold <= 0 switches its test off.  The tests are made in float64 on the float32 harmonics.  Weight of carrier k at a valid
+// node: mode 0: 1; mode 1: |S_k|^2 / S_0, with a reference 1 / (S_0 / |S_k|^2 + R_0 / |R_k|^2) (inverse shot-noise phase variance);
+// 0 where that is not finite and positive.
+constexpr int FR_W_THREADS = 256;
+constexpr int FR_W_MAXBLOCKS = 256;   // partial maxima per frame
+
+__device__ __forceinline__ double fr_abs2(float2 a) { return (double)a.x * (double)a.x + (double)a.y * (double)a.y; }
+
+static int fr_w_blocks(long long plane) {
+    const long long b = (plane + FR_W_THREADS - 1) / FR_W_THREADS;
+    return (int)(b < FR_W_MAXBLOCKS ? b : FR_W_MAXBLOCKS);
+}
+
+// stage 1 of the frame maximum of plane 0: workgroup b of frame m strides over the nodes and writes part[m nb + b].  A maximum
+// does not depend on the order it is taken in; non-finite values never win a comparison (-inf for a frame without a finite one).
+// grid (nb, frames of S, 2): z = 1 takes the reference, which has nr frames
+__global__ void __launch_bounds__(FR_W_THREADS) k_fr_level_partials(const float2* __restrict__ S, const float2* __restrict__ R, int nr,
+                                                                    long long frame_stride, int plane, int nb, float* __restrict__ part_s,
+                                                                    float* __restrict__ part_r) {
+    __shared__ float sh[FR_W_THREADS / 64];
+    const int m = blockIdx.y, ref = blockIdx.z;
+    if (ref && (!R || m >= nr)) return;
+    const float2* __restrict__ h = (ref ? R : S) + (size_t)m * frame_stride;
+    float best = -INFINITY;
+    for (int e = blockIdx.x * FR_W_THREADS + threadIdx.x; e < plane; e += nb * FR_W_THREADS) {
+        const float v = h[e].x;
+        if (v > best && v < INFINITY) best = v;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_down(best, o, 64));
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < FR_W_THREADS / 64; ++w) best = fmaxf(best, sh[w]);
+        (ref ? part_r : part_s)[(size_t)m * nb + blockIdx.x] = best;
+    }
+}
+
+// stage 2 (every workgroup of a frame takes the maximum of its nb partials in index order) and the weights.  grid (ceil(plane / 256), n)
+__global__ void __launch_bounds__(FR_W_THREADS) k_fr_weights(const float2* __restrict__ S, const float2* __restrict__ R, long long r_stride,
+                                                             int K, int plane, int nb, const float* __restrict__ part_s,
+                                                             const float* __restrict__ part_r, double min_level, double min_vis, int mode,
+                                                             float* __restrict__ w_out) {
+    __shared__ float top[2];
+    const size_t m = blockIdx.y;
+    if (threadIdx.x < 2 && min_level > 0.0) {     // without a level test there are no partials
+        const float* __restrict__ part = threadIdx.x == 0 ? part_s + m * nb : part_r + (r_stride ? m * nb : 0);
+        float best = -INFINITY;
+        if (threadIdx.x == 0 || R)
+            for (int b = 0; b < nb; ++b) best = fmaxf(best, part[b]);
+        top[threadIdx.x] = best;
+    }
+    __syncthreads();
+    const int e = blockIdx.x * FR_W_THREADS + threadIdx.x;
+    if (e >= plane) return;
+    const float2* __restrict__ s = S + m * (size_t)(K + 1) * plane + e;
+    const float2* __restrict__ r = R ? R + m * r_stride + e : nullptr;
+    const double s0 = (double)s[0].x, r0 = r ? (double)r[0].x : 1.0;
+    bool ok = true;
+    if (min_level > 0.0) ok = s0 >= min_level * (double)top[0] && (!r || r0 >= min_level * (double)top[1]);
+    if (min_vis > 0.0)
+        for (int k = 0; k < K; ++k) {
+            ok = ok && 2.0 * sqrt(fr_abs2(s[(size_t)(k + 1) * plane])) / s0 >= min_vis;
+            if (r) ok = ok && 2.0 * sqrt(fr_abs2(r[(size_t)(k + 1) * plane])) / r0 >= min_vis;
+        }
+    for (int k = 0; k < K; ++k) {     // the validity is that of all carriers, the value that of carrier k
+        double inv = s0 / fr_abs2(s[(size_t)(k + 1) * plane]);
+        if (r) inv += r0 / fr_abs2(r[(size_t)(k + 1) * plane]);
+        const float v = mode == 0 ? 1.f : (float)(1.0 / inv);
+        w_out[(m * K + k) * plane + e] = (ok && v > 0.f && isfinite(v)) ? v : 0.f;
+    }
+}
+
+// k_fr_shift from a wrapped map and its unwrapped copy: the float32 unwrapped phase carries half a spacing of up to tens of radians,
+// so the phase is formed again in float64 as wrapped + 2 pi round((unwrapped - wrapped) / 2 pi); NaN where the unwrapped map is NaN.
+__global__ void __launch_bounds__(256) k_fr_shift_levels(const float* __restrict__ w1, const float* __restrict__ w2,
+                                                         const float* __restrict__ u1, const float* __restrict__ u2, long long stride,
+                                                         int plane, double m00, double m01, double m10, double m11,
+                                                         double* __restrict__ dy, double* __restrict__ dx) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= plane) return;
+    const size_t m = blockIdx.y;
+    const double wa = (double)w1[m * stride + e], wb = (double)w2[m * stride + e];
+    const double a = wa + 2.0 * M_PI * rint(((double)u1[m * stride + e] - wa) * (0.5 * M_1_PI));
+    const double b = wb + 2.0 * M_PI * rint(((double)u2[m * stride + e] - wb) * (0.5 * M_1_PI));
+    dy[m * plane + e] = -(m00 * a + m01 * b) * (0.5 * M_1_PI);
+    dx[m * plane + e] = -(m10 * a + m11 * b) * (0.5 * M_1_PI);
+}
+
+static int fr_check_shift(const void* p1, const void* p2, long long stride, int n, int gy, int gx, const double* minv, const void* dy,
+                          const void* dx) {
+    if (!p1 || !p2 || !minv || !dy || !dx) return fail(B4D_EINVAL, "null argument");
+    if (n < 1 || gy < 1 || gx < 1) return fail(B4D_EINVAL, "fringe: map count and sides must be >= 1");
+    if (n > 65535) return fail(B4D_ESIZE, "fringe: at most 65535 maps per call");
+    const long long plane = (long long)gy * gx;
+    if (plane > (1LL << 28)) return fail(B4D_ESIZE, "fringe: grids are limited to 2^28 nodes");
+    if (stride < plane) return fail(B4D_EINVAL, "fringe: the map stride is at least gy * gx");
+    for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(minv[k])) return fail(B4D_EINVAL, "fringe: the inverse carrier matrix must be finite");
+    return B4D_OK;
+}
+
 static int fr_check(int n, int K, int H, int W, int wy, int wx, int sty, int stx) {
     if (n < 1 || H < 1 || W < 1) return fail(B4D_EINVAL, "fringe: frame count and sides must be >= 1");
     if (n > 65535) return fail(B4D_ESIZE, "fringe: at most 65535 frames per call");
@@ -309,18 +414,57 @@ extern "C" int b4d_fringe_compare(const void* sample, const void* reference, lon
     return B4D_OK;
 }
 
-extern "C" int b4d_fringe_shift(const float* phase1, const float* phase2, long long stride, int n, int gy, int gx, const double* minv,
-                                double* dy, double* dx, void* stream) {
-    if (!phase1 || !phase2 || !minv || !dy || !dx) return fail(B4D_EINVAL, "null argument");
+extern "C" size_t b4d_fringe_weights_workspace_bytes(int n, int gy, int gx) {
+    if (n < 1 || n > 65535 || gy < 1 || gx < 1 || (long long)gy * gx > (1LL << 28)) return 0;
+    return 2 * fr_align256((size_t)n * fr_w_blocks((long long)gy * gx) * sizeof(float));
+}
+
+extern "C" int b4d_fringe_weights(const void* sample, const void* reference, long long reference_stride, int n, int n_carriers, int gy,
+                                  int gx, double min_level, double min_visibility, int mode, float* w_out, void* workspace,
+                                  void* stream) {
+    if (!sample || !w_out || !workspace) return fail(B4D_EINVAL, "null argument");
     if (n < 1 || gy < 1 || gx < 1) return fail(B4D_EINVAL, "fringe: map count and sides must be >= 1");
     if (n > 65535) return fail(B4D_ESIZE, "fringe: at most 65535 maps per call");
+    if (n_carriers < 1 || n_carriers > FR_MAX_K) return fail(B4D_EINVAL, "fringe: 1 .. " + std::to_string(FR_MAX_K) + " carriers");
     const long long plane = (long long)gy * gx;
     if (plane > (1LL << 28)) return fail(B4D_ESIZE, "fringe: grids are limited to 2^28 nodes");
-    if (stride < plane) return fail(B4D_EINVAL, "fringe: the map stride is at least gy * gx");
-    for (int k = 0; k < 4; ++k)
-        if (!std::isfinite(minv[k])) return fail(B4D_EINVAL, "fringe: the inverse carrier matrix must be finite");
+    if (!reference) reference_stride = 0;
+    if (reference_stride != 0 && reference_stride != (n_carriers + 1) * plane)
+        return fail(B4D_EINVAL, "fringe: reference_stride is 0 (shared reference) or (n_carriers + 1) * gy * gx (paired)");
+    if (!(min_level >= 0.0 && min_level <= 1.0)) return fail(B4D_EINVAL, "fringe: min_level lies in 0 .. 1");
+    if (!(min_visibility >= 0.0 && std::isfinite(min_visibility))) return fail(B4D_EINVAL, "fringe: min_visibility is finite and >= 0");
+    if (mode != 0 && mode != 1) return fail(B4D_EINVAL, "fringe: weight mode is 0 (mask) or 1 (inverse phase variance)");
+    hipStream_t st = (hipStream_t)stream;
+    const int nb = fr_w_blocks(plane);
+    float* part_s = (float*)workspace;
+    float* part_r = (float*)((char*)workspace + fr_align256((size_t)n * nb * sizeof(float)));
+    if (min_level > 0.0)
+        hipLaunchKernelGGL(k_fr_level_partials, dim3(nb, n, reference ? 2 : 1), dim3(FR_W_THREADS), 0, st, (const float2*)sample,
+                           (const float2*)reference, reference_stride ? n : 1, (n_carriers + 1) * plane, (int)plane, nb, part_s, part_r);
+    hipLaunchKernelGGL(k_fr_weights, dim3((unsigned)((plane + FR_W_THREADS - 1) / FR_W_THREADS), n), dim3(FR_W_THREADS), 0, st,
+                       (const float2*)sample, (const float2*)reference, reference_stride, n_carriers, (int)plane, nb,
+                       (const float*)part_s, (const float*)part_r, min_level, min_visibility, mode, w_out);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+
+extern "C" int b4d_fringe_shift(const float* phase1, const float* phase2, long long stride, int n, int gy, int gx, const double* minv,
+                                double* dy, double* dx, void* stream) {
+    if (const int rc = fr_check_shift(phase1, phase2, stride, n, gy, gx, minv, dy, dx)) return rc;
+    const long long plane = (long long)gy * gx;
     hipLaunchKernelGGL(k_fr_shift, dim3((unsigned)((plane + 255) / 256), n), dim3(256), 0, (hipStream_t)stream, phase1, phase2, stride,
                        (int)plane, minv[0], minv[1], minv[2], minv[3], dy, dx);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+
+extern "C" int b4d_fringe_shift_levels(const float* wrapped1, const float* wrapped2, const float* unwrapped1, const float* unwrapped2,
+                                       long long stride, int n, int gy, int gx, const double* minv, double* dy, double* dx, void* stream) {
+    if (!unwrapped1 || !unwrapped2) return fail(B4D_EINVAL, "null argument");
+    if (const int rc = fr_check_shift(wrapped1, wrapped2, stride, n, gy, gx, minv, dy, dx)) return rc;
+    const long long plane = (long long)gy * gx;
+    hipLaunchKernelGGL(k_fr_shift_levels, dim3((unsigned)((plane + 255) / 256), n), dim3(256), 0, (hipStream_t)stream, wrapped1, wrapped2,
+                       unwrapped1, unwrapped2, stride, (int)plane, minv[0], minv[1], minv[2], minv[3], dy, dx);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }

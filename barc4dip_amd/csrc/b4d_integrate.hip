@@ -1,5 +1,6 @@
 // b4d_integrate.hip -- wavefront reconstruction: least-squares integration of a slope field on a regular grid and the
-// low-order (6-term quadratic) fit of the result.
+// low-order (6-term quadratic) fit of the result; the weighted variants (section 14) and the phase unwraps
+// that share their solvers (sections 17 and 18).
 //
 // Southwell geometry: the slope on the edge between two neighbouring nodes is the mean of the two node slopes; phi is the
 // zero-mean minimiser of the squared edge residuals.  The normal equations are a 5-point Neumann Laplacian, which the
@@ -797,6 +798,143 @@ __global__ void __launch_bounds__(256) k_wf_unwrap_congruence(const float* __res
     out[fo + e] = k == 0.f ? v : (float)((double)v + 6.283185307179586 * (double)k);
 }
 
+// ---- the PCG loop of section 14, shared by the weighted integration and the weighted unwrap.  A setup kernel has written weff, cy,
+// cx, r = b, x = 0 and the partials of |b|^2 into part_a; x is the solution, started at 0.  Ends with k_wf_wfinish.  The caller
+// holds wf_mutex() (the basis pointers stay valid until the launches are queued).
+static int wf_pcg_solve(const WfPcg& g, const WfBasis* by, const WfBasis* bx, double hy, double hx, int max_iter, int nan_invalid,
+                        float* x, int* iterations, double* residual, hipStream_t st) {
+    const int n = g.n, ny = g.ny, nx = g.nx;
+    const dim3 grid(g.nb, n), block(WF_PCG_THREADS);
+    wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, nullptr, st);
+    hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, 0, 1);
+    hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, 0, 1);
+    std::vector<int> flags(n);
+    int done = 0;
+    while (done < max_iter) {
+        const int slot = done & 1;
+        hipLaunchKernelGGL(k_wf_wapply, grid, block, 0, st, g, slot);
+        hipLaunchKernelGGL(k_wf_wupdate, grid, block, 0, st, g, slot, x);
+        wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, g.flags, st);      // frozen maps cost no products
+        hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, slot, 0);
+        hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, slot, 0);
+        ++done;
+        if (done % WF_PCG_CHECK == 0 && done < max_iter) {   // every map frozen: stop early (one small copy and a wait)
+            B4D_HIP(hipMemcpyAsync(flags.data(), g.flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
+            B4D_HIP(hipStreamSynchronize(st));
+            bool all = true;
+            for (int m = 0; m < n && all; ++m) all = flags[m] != 0;
+            if (all) break;
+        }
+    }
+    hipLaunchKernelGGL(k_wf_wfinish, grid, block, 0, st, g, done & 1, nan_invalid, x, iterations, residual);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
+
+// ---- weighted / masked unwrapping: the weighted normal equations of section 14 with the wrapped differences
+// as edge slopes (unit spacings), then the congruence step against a seed node chosen among the valid ones.
+// effective weight of a node: 0 unless the weight is finite and positive and the phase is finite
+__device__ __forceinline__ float wf_unwrap_weff(const float* __restrict__ w, const float* __restrict__ ph, int e) {
+    const float a = w[e];
+    return (a > 0.f && isfinite(a) && isfinite(ph[e])) ? a : 0.f;
+}
+
+// once per call, as k_wf_wsetup: effective weights, edge coefficients, b = weighted divergence of the wrapped differences, x = 0,
+// partials of |b|^2.  A difference is formed only across an edge of positive coefficient, so the phase of a weight-0 node (NaN
+// included) passes through isfinite alone.
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_unwrap_wsetup(const float* __restrict__ phase, const float* __restrict__ w,
+                                                                     long long w_stride, WfPcg g, float* __restrict__ x) {
+    __shared__ double sh[WF_PCG_THREADS / 64][1];
+    const int map = blockIdx.y, ny = g.ny, nx = g.nx, plane = ny * nx;
+    const size_t fo = (size_t)map * plane;
+    const float* __restrict__ ph = phase + fo;
+    const float* __restrict__ mw = w + (long long)map * w_stride;
+    double s[1] = {0.0};
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS) {
+        const int i = e / nx, j = e % nx;
+        const float w0 = wf_unwrap_weff(mw, ph, e);
+        const float hd = i + 1 < ny ? wf_hmean(w0, wf_unwrap_weff(mw, ph, e + nx)) : 0.f;
+        const float hu = i > 0 ? wf_hmean(w0, wf_unwrap_weff(mw, ph, e - nx)) : 0.f;
+        const float hr = j + 1 < nx ? wf_hmean(w0, wf_unwrap_weff(mw, ph, e + 1)) : 0.f;
+        const float hl = j > 0 ? wf_hmean(w0, wf_unwrap_weff(mw, ph, e - 1)) : 0.f;
+        float by = 0.f, bx = 0.f;
+        if (hu > 0.f) by += hu * wf_wrap(ph[e] - ph[e - nx]);
+        if (hd > 0.f) by -= hd * wf_wrap(ph[e + nx] - ph[e]);
+        if (hl > 0.f) bx += hl * wf_wrap(ph[e] - ph[e - 1]);
+        if (hr > 0.f) bx -= hr * wf_wrap(ph[e + 1] - ph[e]);
+        const float b = by + bx;
+        g.weff[fo + e] = w0;
+        g.cy[fo + e] = hd;
+        g.cx[fo + e] = hr;
+        g.r[fo + e] = b;
+        x[fo + e] = 0.f;
+        s[0] += (double)b * (double)b;
+    }
+    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
+}
+
+// seed node of a map: the valid node of largest weight, ties to the smallest (i - ny/2)^2 + (j - nx/2)^2, then to the smallest
+// index.  The three keys order the nodes totally, so the winner does not depend on the order of the comparisons; they are made
+// in a fixed order all the same (lane stride, then a tree over the workgroup in LDS).  One workgroup per map; seed = -1 and
+// shift = 0 for a map without a valid node, else shift = phase[seed] - p[seed].
+struct WfSeed {
+    float w;
+    int d, e;
+};
+__device__ __forceinline__ bool wf_seed_better(const WfSeed& a, const WfSeed& b) {   // a before b
+    if (a.w != b.w) return a.w > b.w;
+    if (a.d != b.d) return a.d < b.d;
+    return a.e < b.e;
+}
+
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_unwrap_seed(const float* __restrict__ phase, WfPcg g, const float* __restrict__ p,
+                                                                   int* __restrict__ seed, float* __restrict__ shift) {
+    __shared__ WfSeed sh[WF_PCG_THREADS];
+    const int map = blockIdx.x, ny = g.ny, nx = g.nx, plane = ny * nx;
+    const size_t fo = (size_t)map * plane;
+    WfSeed best{0.f, 0x7fffffff, 0x7fffffff};
+    for (int e = threadIdx.x; e < plane; e += WF_PCG_THREADS) {
+        const int di = e / nx - ny / 2, dj = e % nx - nx / 2;
+        const WfSeed c{g.weff[fo + e], di * di + dj * dj, e};
+        if (c.w > 0.f && wf_seed_better(c, best)) best = c;
+    }
+    sh[threadIdx.x] = best;
+    __syncthreads();
+    for (int o = WF_PCG_THREADS / 2; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o && wf_seed_better(sh[threadIdx.x + o], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const bool any = sh[0].w > 0.f;
+        seed[map] = any ? sh[0].e : -1;
+        shift[map] = any ? phase[fo + sh[0].e] - p[fo + sh[0].e] : 0.f;
+    }
+}
+
+// in place on the solution p (= out): out = ph + 2 pi round((p + shift - ph) / 2 pi) at the valid nodes, a node that keeps its
+// level keeps its bits; weight-0 nodes get NaN or the levelled p + shift; a map without a valid node is NaN throughout
+__global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_unwrap_wcongruence(const float* __restrict__ phase, WfPcg g,
+                                                                          const int* __restrict__ seed, const float* __restrict__ shift,
+                                                                          int nan_invalid, float* __restrict__ out) {
+    const int map = blockIdx.y, plane = g.ny * g.nx;
+    const size_t fo = (size_t)map * plane;
+    const bool none = seed[map] < 0;
+    const float sf = shift[map];
+    for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS) {
+        const float p = out[fo + e] + sf;
+        float r;
+        if (g.weff[fo + e] > 0.f) {
+            const float v = phase[fo + e];
+            const float k = rintf((p - v) * 0.15915494309189535f);
+            r = k == 0.f ? v : (float)((double)v + 6.283185307179586 * (double)k);
+        } else {
+            r = (nan_invalid || none) ? __builtin_nanf("") : p;
+        }
+        out[fo + e] = r;
+    }
+}
+
 }  // namespace b4d
 
 using namespace b4d;
@@ -893,30 +1031,42 @@ extern "C" int b4d_integrate_gradient_weighted(const float* gy, const float* gx,
     const WfBasis *by = nullptr, *bx = nullptr;
     if (const int rc = wf_basis(ny, ny, &by)) return rc;
     if (const int rc = wf_basis(nx, ny, &bx)) return rc;
+    hipLaunchKernelGGL(k_wf_wsetup, dim3(g.nb, n), dim3(WF_PCG_THREADS), 0, st, gy, gx, w, w_stride, (float)(1.0 / hy),
+                       (float)(1.0 / hx), g, out);
+    return wf_pcg_solve(g, by, bx, hy, hx, max_iter, nan_invalid, out, iterations, residual, st);
+}
+
+extern "C" size_t b4d_phase_unwrap_weighted_workspace_bytes(int n, int ny, int nx) {
+    if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
+    WfPcg g;
+    return wf_pcg_layout(nullptr, n, ny, nx, g) + 2 * wf_align256((size_t)n * sizeof(int));
+}
+
+extern "C" int b4d_phase_unwrap_weighted(const float* phase, const float* w, long long w_stride, int n, int ny, int nx, double rtol,
+                                         int max_iter, int nan_invalid, void* workspace, float* out, int* iterations, double* residual,
+                                         void* stream) {
+    if (!phase || !w || !workspace || !out || !iterations || !residual) return fail(B4D_EINVAL, "null argument");
+    if (phase == out) return fail(B4D_EINVAL, "unwrap: out must not be the input");
+    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
+    const long long plane = (long long)ny * nx;
+    if (w_stride != 0 && w_stride != plane) return fail(B4D_EINVAL, "w_stride is 0 (shared weights) or ny * nx (per map)");
+    if (!(rtol >= 0.0 && std::isfinite(rtol))) return fail(B4D_EINVAL, "rtol must be finite and >= 0");
+    if (max_iter < 0) return fail(B4D_EINVAL, "max_iter must be >= 0");
+    hipStream_t st = (hipStream_t)stream;
+    WfPcg g;
+    char* tail = (char*)workspace + wf_pcg_layout((char*)workspace, n, ny, nx, g);
+    int* seed = (int*)tail;
+    float* shift = (float*)(tail + wf_align256((size_t)n * sizeof(int)));
+    g.tol2 = rtol * rtol;
+    std::lock_guard<std::mutex> lk(wf_mutex());     // basis pointers stay valid until the launches below are queued
+    const WfBasis *by = nullptr, *bx = nullptr;
+    if (const int rc = wf_basis(ny, ny, &by)) return rc;
+    if (const int rc = wf_basis(nx, ny, &bx)) return rc;
     const dim3 grid(g.nb, n), block(WF_PCG_THREADS);
-    hipLaunchKernelGGL(k_wf_wsetup, grid, block, 0, st, gy, gx, w, w_stride, (float)(1.0 / hy), (float)(1.0 / hx), g, out);
-    wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, nullptr, st);
-    hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, 0, 1);
-    hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, 0, 1);
-    std::vector<int> flags(n);
-    int done = 0;
-    while (done < max_iter) {
-        const int slot = done & 1;
-        hipLaunchKernelGGL(k_wf_wapply, grid, block, 0, st, g, slot);
-        hipLaunchKernelGGL(k_wf_wupdate, grid, block, 0, st, g, slot, out);
-        wf_poisson(by, bx, g.r, g.t, g.qz, n, ny, nx, hy, hx, g.flags, st);      // frozen maps cost no products
-        hipLaunchKernelGGL(k_wf_wdot, grid, block, 0, st, g, slot, 0);
-        hipLaunchKernelGGL(k_wf_wdirection, grid, block, 0, st, g, slot, 0);
-        ++done;
-        if (done % WF_PCG_CHECK == 0 && done < max_iter) {   // every map frozen: stop early (one small copy and a wait)
-            B4D_HIP(hipMemcpyAsync(flags.data(), g.flags, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, st));
-            B4D_HIP(hipStreamSynchronize(st));
-            bool all = true;
-            for (int m = 0; m < n && all; ++m) all = flags[m] != 0;
-            if (all) break;
-        }
-    }
-    hipLaunchKernelGGL(k_wf_wfinish, grid, block, 0, st, g, done & 1, nan_invalid, out, iterations, residual);
+    hipLaunchKernelGGL(k_wf_unwrap_wsetup, grid, block, 0, st, phase, w, w_stride, g, out);
+    if (const int rc = wf_pcg_solve(g, by, bx, 1.0, 1.0, max_iter, 0, out, iterations, residual, st)) return rc;
+    hipLaunchKernelGGL(k_wf_unwrap_seed, dim3(n), block, 0, st, phase, g, (const float*)out, seed, shift);
+    hipLaunchKernelGGL(k_wf_unwrap_wcongruence, grid, block, 0, st, phase, g, (const int*)seed, (const float*)shift, nan_invalid, out);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }

@@ -448,7 +448,8 @@ int b4d_focal_spot(b4d_plan* general_plan, const float* err, const float* amp, l
  *   of neighbouring nodes along y and x are the edge slopes of the 5-point Neumann Poisson problem of b4d_integrate_gradient
  *   (unit spacings, no Southwell means); its zero-mean solution p, shifted to equal the input at node (ny / 2, nx / 2), selects
  *   the level: out = phase + 2 pi round((p - phase) / 2 pi).  The data are never smoothed, and a node whose level is 0 keeps its
- *   bits.  Whole-grid and unweighted: a node that is not finite spoils its map.  phase, out: DEVICE (n, ny, nx) float32, distinct;
+ *   bits.  Whole-grid and unweighted: a node that is not finite spoils its map (b4d_phase_unwrap_weighted below takes weights
+ *   and masks).  phase, out: DEVICE (n, ny, nx) float32, distinct;
  *   workspace: DEVICE, b4d_phase_unwrap_workspace_bytes(n, ny, nx) bytes (0 for an unsupported shape).  Sides 1 .. 2048
  *   (B4D_ESIZE beyond), n <= 65535.
  * b4d_fringe_shift: (dy, dx) = -Minv (phase1, phase2) / 2 pi per node, in float64.  minv: HOST 4 float64, row-major inverse of
@@ -464,6 +465,41 @@ size_t b4d_phase_unwrap_workspace_bytes(int n, int ny, int nx);
 int b4d_phase_unwrap(const float* phase, int n, int ny, int nx, void* workspace, float* out, void* stream);
 int b4d_fringe_shift(const float* phase1, const float* phase2, long long stride, int n, int gy, int gx, const double* minv, double* dy,
                      double* dx, void* stream);
+
+/* Weighted and masked phase unwrapping.
+ * b4d_phase_unwrap_weighted: b4d_phase_unwrap with a weight w >= 0 per node (layout, w_stride, limits, rtol, max_iter, iterations
+ *   and residual as b4d_integrate_gradient_weighted, and the same conjugate-gradient solver).  A node whose weight is not finite
+ *   and positive, or whose phase is not finite, has weight 0 and its phase is never read into a result.  Edge weights are the
+ *   harmonic means of the node weights, edge slopes the wrapped differences (unit spacings), and p minimises
+ *     sum wy (p[i+1][j] - p[i][j] - W(phase[i+1][j] - phase[i][j]))^2 + sum wx (p[i][j+1] - p[i][j] - W(phase[i][j+1] - phase[i][j]))^2
+ *   in the gauge of section 14.  Seed node: the valid node of largest weight, ties to the smallest (i - ny/2)^2 + (j - nx/2)^2, then
+ *   to the smallest row-major index (with equal weights: node (ny / 2, nx / 2)).  p is shifted to equal the input at the seed and
+ *   out = phase + 2 pi round((p - phase) / 2 pi) at the valid nodes; a valid node whose level is 0 keeps its bits.  Weight-0 nodes
+ *   get NaN (nan_invalid != 0) or the shifted p.  Pieces of the valid region that no edge connects are levelled against each
+ *   other as smoothly as possible: their relative level is NOT measured.  A map without a valid node is NaN, 0 iterations.
+ *   phase, out: DEVICE (n, ny, nx) float32, distinct.  workspace: DEVICE, b4d_phase_unwrap_weighted_workspace_bytes(n, ny, nx)
+ *   bytes (0 for an unsupported shape), 256-byte aligned; after the call its first n * ny * nx floats hold the effective node
+ *   weights.  The call waits for `stream` every 4 iterations, as the weighted integration does.
+ * b4d_fringe_weights: node weights of the phase maps from the harmonic maps of b4d_fringe_demodulate (sample, reference and
+ *   reference_stride as b4d_fringe_compare; reference may be NULL).  A node is valid if S_0 >= min_level * (largest finite S_0 of
+ *   its frame), likewise R_0 within the reference frame, and if every visibility 2 |S_k| / S_0 and 2 |R_k| / R_0, over all
+ *   carriers, is >= min_visibility; a threshold of 0 switches its test off (0 <= min_level <= 1, min_visibility >= 0).  The tests
+ *   are made in float64.  w_out: DEVICE (n, n_carriers, gy, gx) float32, 0 at nodes that are not valid, else for carrier k
+ *     mode 0: 1      mode 1: 1 / (S_0 / |S_k|^2 + R_0 / |R_k|^2), without a reference |S_k|^2 / S_0
+ *   (the inverse shot-noise variance of the phase up to a constant), 0 where that is not finite and positive.  The frame maxima
+ *   are reduced in two stages on the device.  workspace: DEVICE, b4d_fringe_weights_workspace_bytes(n, gy, gx) bytes.
+ * b4d_fringe_shift_levels: b4d_fringe_shift from the wrapped maps and their unwrapped copies (all DEVICE float32, map m at offset
+ *   m * stride): the phase is formed again in float64 as wrapped + 2 pi round((unwrapped - wrapped) / 2 pi), so the half spacing
+ *   that the float32 unwrapped phase carries at tens of radians does not reach the shift; NaN where an unwrapped map is NaN.
+ * All are asynchronous on `stream` apart from the waits named above and have no host fallback. */
+size_t b4d_phase_unwrap_weighted_workspace_bytes(int n, int ny, int nx);
+int b4d_phase_unwrap_weighted(const float* phase, const float* w, long long w_stride, int n, int ny, int nx, double rtol, int max_iter,
+                              int nan_invalid, void* workspace, float* out, int* iterations, double* residual, void* stream);
+size_t b4d_fringe_weights_workspace_bytes(int n, int gy, int gx);
+int b4d_fringe_weights(const void* sample, const void* reference, long long reference_stride, int n, int n_carriers, int gy, int gx,
+                       double min_level, double min_visibility, int mode, float* w_out, void* workspace, void* stream);
+int b4d_fringe_shift_levels(const float* wrapped1, const float* wrapped2, const float* unwrapped1, const float* unwrapped2,
+                            long long stride, int n, int gy, int gx, const double* minv, double* dy, double* dx, void* stream);
 
 #ifdef __cplusplus
 }
