@@ -501,6 +501,39 @@ int b4d_fringe_weights(const void* sample, const void* reference, long long refe
 int b4d_fringe_shift_levels(const float* wrapped1, const float* wrapped2, const float* unwrapped1, const float* unwrapped2,
                             long long stride, int n, int gy, int gx, const double* minv, double* dy, double* dx, void* stream);
 
+/* Transmission and dark-field maps of speckle tracking (barc4dip_amd.signal.speckle_contrast): the weighted
+ * moments of every window of a reference frame and of the image window that its tracked displacement points at.
+ * Grid and pairing are those of b4d_displacement_map with margin in the place of search: origins y0 = margin_y + k * step_y for
+ * every k with y0 + win_y + margin_y <= h, likewise for x; pair z compares reference frame pair_ref[z] with image frame
+ * pair_img[z] (HOST int32, read before the call returns); ref (nref, h, w), img (nimg, h, w): DEVICE float32.
+ * dy, dx: DEVICE float64 displacements in pixels.  LAYOUT: field_stride is the offset (in doubles) from the field of one pair to
+ * that of the next and must be n * gy * gx with an integer n >= 1 (B4D_EINVAL otherwise); n is the stride between neighbouring
+ * nodes: node (Y, X) of pair z is read at dy[z * field_stride + (Y * gx + X) * n], the same for dx.  Two planar (npairs, gy, gx)
+ * maps have field_stride = gy * gx; the (npairs, gy, gx, 4) output `o` of b4d_displacement_map is passed without a copy as
+ * dy = o, dx = o + 1, field_stride = 4 * gy * gx.
+ * Per window: r[j][i] = ref[y0+j][x0+i]; s[j][i] = the image at (y0 + j + dy, x0 + i + dx), the convention of
+ * b4d_warp_grid: the image window displaced by the tracked shift matches the reference window.  order 0 takes the pixel at
+ * floor(d + 0.5) per axis; order 1 is bilinear with the taps floor(d), floor(d) + 1 and the weights 1 - f, f for
+ * f = d - floor(d), formed and combined in float64; a tap whose weight is exactly 0 is not read.  taper 0 is flat, 1 the
+ * half-sample Hann h_w[j] = 0.5 - 0.5 cos(2 pi (j + 0.5) / w) per axis.  With the weights h[j][i] = h_wy[j] h_wx[i] normalised
+ * to sum 1 the weighted means Rm, Sm, variances VR, VS and covariance C are formed in float64 from power sums shifted by the
+ * window's first pixel.  out: DEVICE (npairs, gy, gx, 6) float64
+ *   0 transmission = Sm / Rm                         3 correlation = C / sqrt(VS VR)
+ *   1 dark_field = (sqrt(VS) / Sm) / (sqrt(VR) / Rm)   4 visibility_ref = sqrt(VR) / Rm
+ *   2 dark_field_fit = C / (VR transmission)         5 visibility = sqrt(VS) / Sm
+ * dark_field is the visibility ratio (noise raises it), dark_field_fit the least-squares slope of s on r over the transmission.
+ * A quantity whose denominator is not above 0 is NaN, and so is the square root of a variance that is not above 0: a window
+ * without contrast (a single pixel, a constant patch) has a transmission and nothing else.  A window whose displacement is not
+ * finite, or whose taps of non-zero weight would leave [0, h - 1] x [0, w - 1], gets six NaNs and no address is formed for it;
+ * |d| <= margin always stays inside.  One launch, grid (gx, gy, npairs), one workgroup per window, on `stream`; the summation
+ * order depends on the window shape alone, so a frame gives the same bits alone and inside any batch.
+ * Limits: 1 <= win <= 128 and 0 <= margin <= 32 per axis (B4D_ESIZE beyond), step >= 1, order and taper 0 or 1, at least one
+ * window (B4D_EINVAL otherwise), gy and npairs <= 65535.  All argument errors are returned before any launch.              */
+int b4d_speckle_contrast(const float* ref, int nref, const float* img, int nimg, const int32_t* pair_ref,
+                         const int32_t* pair_img, int npairs, int h, int w, int win_y, int win_x, int step_y, int step_x,
+                         int margin_y, int margin_x, const double* dy, const double* dx, long long field_stride, int order,
+                         int taper, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
