@@ -102,6 +102,10 @@ SIGNATURES = {
     "b4d_fringe_weights": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _d, _d, _i, _vp, _vp, _vp]),
     "b4d_fringe_shift_levels": (_i, [_vp, _vp, _vp, _vp, C.c_longlong, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "b4d_speckle_contrast": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, C.c_longlong, _i, _i, _vp, _vp]),
+    "b4d_two_time_workspace_bytes": (_sz, [_i, C.c_longlong, _i, _i]),
+    "b4d_two_time": (_i, [_vp, _i, C.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b4d_two_time_timed": (_i, [_vp, _i, C.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b4d_two_time_lags": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

@@ -534,6 +534,48 @@ int b4d_speckle_contrast(const float* ref, int nref, const float* img, int nimg,
                          int margin_y, int margin_x, const double* dy, const double* dx, long long field_stride, int order,
                          int taper, double* out, void* stream);
 
+/* Two-time correlation of a speckle stack (barc4dip_amd.metrics.two_time_correlation).
+ * Input is a stack x[t, p] of T >= 2 frames, p over the npix = H W pixels, and an optional label map: label 0 takes no part,
+ * labels 1 .. R name regions (q-rings, mirror zones, detector modules); values outside 0 .. R count as 0.  Region r is the set
+ * P_r of pixels that carry label r and are FINITE IN ALL T FRAMES, N_r = |P_r|.  Per region, in exact arithmetic:
+ *   m_i    = (1/N) sum_p x_ip                          var_i = cov_ii
+ *   cov_ij = (1/N) sum_p (x_ip - m_i)(x_jp - m_j)      contrast_i = sqrt(var_i) / m_i
+ *   norm B4D_TWO_TIME_PEARSON:    C_ij = cov_ij / sqrt(var_i var_j)
+ *   norm B4D_TWO_TIME_INTENSITY:  C_ij = 1 + cov_ij / (m_i m_j)     (= <I_i I_j> / (<I_i><I_j>), the XPCS two-time function)
+ *   norm B4D_TWO_TIME_COVARIANCE: C_ij = cov_ij
+ *   g2[tau]     = mean of C_ij over the computed entries with j - i = tau (n_tau = T - tau of them), tau = 0 .. L
+ *   g2_err[tau] = population standard deviation of those entries / sqrt(n_tau)
+ * A quotient whose denominator is not above 0 is NaN, and so is the square root of a variance that is not above 0: a constant
+ * frame is a NaN row and column under PEARSON but finite under COVARIANCE, a frame of mean 0 is NaN under INTENSITY.  N_r = 0
+ * gives NaN everywhere for that region and n_pixels = 0; it is not an error.  The matrix is exactly symmetric (both triangles
+ * are written from one value); under PEARSON the diagonal is exactly 1.0 wherever var_i > 0.  max_lag = L (0 <= L <= T - 1):
+ * entries with |i - j| > L are NaN, frame-block pairs (blocks of 128 frames) wholly outside the band are not computed, entries
+ * inside the band are bit-identical to the full run.
+ * Arithmetic: the data is centred before the product, Xc = x - c[r][i] with c the float32-rounded mean of the region's pixels
+ * that are finite in frame i; the float32 matrix cores (v_mfma_f32_32x32x2_f32) take the products over chunks of 2048 pixels of
+ * the region's raster-ordered pixel list (float32 chains of 256 products, eight of them added per chunk), and everything across
+ * chunks, the sums s_i of the stored values and the correction
+ * cov_ij = Gc_ij / N - (s_i / N)(s_j / N), m_i = c_i + s_i / N is float64.  Every sum runs in an order fixed by (T, npix,
+ * max_lag) and the region's own pixel list: the same bits from run to run, and for a region alone or among others.
+ * stack: DEVICE (T, npix) float32; labels: DEVICE npix int32 or NULL (then n_regions must be 1 and every pixel is region 1);
+ * two_time: DEVICE (R, T, T) float64; mean, var: DEVICE (R, T) float64; n_pixels: DEVICE (R) int64; workspace: DEVICE,
+ * b4d_two_time_workspace_bytes(T, npix, n_regions, max_lag) bytes (0 for an unsupported shape): the packed centred copy
+ * T (npix / 2048 + R) 2048 floats, one 128 x 128 float tile per (chunk, frame-block pair), and the per-span partial sums.
+ * b4d_two_time_lags reads a matrix stack in that layout.  Asynchronous on `stream`, no host synchronisation.
+ * Limits: 2 <= T <= 2048, R <= 64, npix < 2^31 (B4D_ESIZE beyond); all argument errors are returned before any launch.   */
+#define B4D_TWO_TIME_PEARSON 0
+#define B4D_TWO_TIME_INTENSITY 1
+#define B4D_TWO_TIME_COVARIANCE 2
+size_t b4d_two_time_workspace_bytes(int T, long long npix, int n_regions, int max_lag);
+int b4d_two_time(const float* stack, int T, long long npix, const int* labels, int n_regions, int norm, int max_lag, void* workspace,
+                 double* two_time, double* mean, double* var, long long* n_pixels, void* stream);
+/* The same call with HIP events on `stream` around its stages; waits for the last one.  stage_ms: HOST float[4], the milliseconds
+ * of the scan (labels, sums, offsets), the pack (counts, prefix, packed copy, its sums), the product and the reduction with the
+ * normalisation (tools/bench_two_time.py). */
+int b4d_two_time_timed(const float* stack, int T, long long npix, const int* labels, int n_regions, int norm, int max_lag,
+                       void* workspace, double* two_time, double* mean, double* var, long long* n_pixels, void* stream, float* stage_ms);
+int b4d_two_time_lags(const double* two_time, int n_regions, int T, int max_lag, double* g2, double* g2_err, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
