@@ -106,6 +106,12 @@ SIGNATURES = {
     "b4d_two_time": (_i, [_vp, _i, C.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b4d_two_time_timed": (_i, [_vp, _i, C.c_longlong, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b4d_two_time_lags": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "b4d_multi_tau_workspace_bytes": (_sz, [C.c_longlong, _i, _i, _i, _i]),
+    "b4d_multi_tau_lags": (_i, [C.c_longlong, _i, _i, _vp, _vp, _vp, _vp]),
+    "b4d_multi_tau_scan": (_i, [_vp, _i, C.c_longlong, _vp, _vp]),
+    "b4d_multi_tau_init": (_i, [_vp, _vp, C.c_longlong, _i, _i, _i, _i, _vp, _vp]),
+    "b4d_multi_tau_push": (_i, [_vp, C.c_longlong, _i, C.c_longlong, _i, _i, _i, _i, _vp, _vp]),
+    "b4d_multi_tau_finish": (_i, [C.c_longlong, C.c_longlong, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

@@ -125,22 +125,30 @@ def two_time_correlation(images, *, labels=None, mask=None, norm: str = "pearson
     return out
 
 
-def correlation_decay(result_or_g2, *, level: float = 1.0 / np.e, baseline: float | None = None) -> np.ndarray:
+def correlation_decay(result_or_g2, *, level: float = 1.0 / np.e, baseline: float | None = None, lags=None) -> np.ndarray:
     """Lag at which the normalised lag curve g = (g2 - b) / (g2[0] - b) first falls below ``level``, per region.
 
-    result_or_g2: the dict of ``two_time_correlation`` (then b defaults to 1 for norm "intensity" and to 0 otherwise) or a g2
-    array of shape (L + 1,) or (R, L + 1) (b defaults to 0).  The lag is interpolated linearly between the last lag at or above
-    the level and the first below it; NaN where g never falls below the level.  Returns a float64 array of shape () or (R,)."""
+    result_or_g2: the dict of ``two_time_correlation`` (then b defaults to 1 for norm "intensity" and to 0 otherwise), the dict of
+    ``multi_tau_correlation`` (b defaults to 1), or a g2 array of shape (L + 1,) or (R, L + 1) (b defaults to 0).
+    lags: the delays of the curve's entries, shape (L + 1,), increasing; default ``result["lags"]`` for a dict and 0, 1 .. L for
+    an array.  The lag is interpolated linearly between the last lag at or above the level and the first below it; NaN where g
+    never falls below the level.  Returns a float64 array of shape () or (R,)."""
     if isinstance(result_or_g2, dict):
         g2 = result_or_g2["g2"]
+        meta = result_or_g2.get("meta", {})
         if baseline is None:
-            baseline = 1.0 if result_or_g2.get("meta", {}).get("norm") == "intensity" else 0.0
+            baseline = 1.0 if meta.get("norm") == "intensity" or "lags_per_level" in meta else 0.0
+        if lags is None:
+            lags = result_or_g2.get("lags")
     else:
         g2 = result_or_g2
     b = 0.0 if baseline is None else float(baseline)
     g2 = np.asarray(_host(g2), dtype=np.float64)
     if g2.ndim not in (1, 2) or g2.shape[-1] < 1:
         raise ValueError(f"g2 must have shape (L + 1,) or (R, L + 1), got {g2.shape}")
+    lag = np.arange(g2.shape[-1], dtype=np.float64) if lags is None else np.asarray(_host(lags), dtype=np.float64)
+    if lag.shape != g2.shape[-1:]:
+        raise ValueError(f"lags must have shape {g2.shape[-1:]}, got {lag.shape}")
     rows = np.atleast_2d(g2)
     out = np.full(rows.shape[0], np.nan)
     for r, row in enumerate(rows):
@@ -150,5 +158,5 @@ def correlation_decay(result_or_g2, *, level: float = 1.0 / np.e, baseline: floa
         if below.size == 0:
             continue
         k = int(below[0])
-        out[r] = 0.0 if k == 0 else (k - 1) + (g[k - 1] - level) / (g[k - 1] - g[k])
+        out[r] = lag[0] if k == 0 else lag[k - 1] + (g[k - 1] - level) / (g[k - 1] - g[k]) * (lag[k] - lag[k - 1])
     return out.reshape(g2.shape[:-1])

@@ -576,6 +576,53 @@ int b4d_two_time_timed(const float* stack, int T, long long npix, const int* lab
                        void* workspace, double* two_time, double* mean, double* var, long long* n_pixels, void* stream, float* stage_ms);
 int b4d_two_time_lags(const double* two_time, int n_regions, int T, int max_lag, double* g2, double* g2_err, void* stream);
 
+/* Multi-tau correlation of a long or streamed speckle stack (barc4dip_amd.metrics.multi_tau_correlation).
+ * Input is a stack x[t, p] of T >= 2 frames that arrives in pushes, and an optional label map with the rules of b4d_two_time:
+ * label 0 takes no part, labels 1 .. R name regions, values outside 0 .. R count as 0.  Region r is the set of pixels that carry
+ * label r and are FINITE IN ALL T FRAMES, N their number.  m = lags per level, one of 8, 16, 32.
+ *   Levels.  I_0[k] = x[k], T_0 = T;  I_l[k] = (I_{l-1}[2k] + I_{l-1}[2k+1]) / 2 in float32, T_l = floor(T / 2^l): a last
+ *            unpaired frame of a level never forms a frame of the next.
+ *   Lags.    Level 0 has j = 0 .. m - 1, level l >= 1 has j = m/2 .. m - 1; the delay is tau = j 2^l frames.  Level l >= 1
+ *            exists while T_l >= m/2 + 1, and max_level caps the last level used.  A lag is reported when n = T_l - j >= 1, in
+ *            the order of level, then j.  T = 37, m = 16: 25 lags, delays 0 .. 15, 16, 18 .. 30, 32 (the last with n = 1).
+ *            T = 100 000, m = 16: 116 lags, the last delay 90 112 frames.
+ *   Sums over the region's pixels and k = 0 .. n - 1:
+ *            P = sum I_l[k] I_l[k+j]    Q = sum (I_l[k] I_l[k+j])^2    A = sum I_l[k]    B = sum I_l[k+j]
+ *   g2     = (P / Nn) / ((A / Nn)(B / Nn))                                 (the symmetric normalisation)
+ *   g2_err = sqrt(max(Q / Nn - (P / Nn)^2, 0) / (Nn)) / ((A / Nn)(B / Nn)) (the standard error of the mean product IF the products
+ *            were independent: a lower bound on the real error)
+ *   mean[r] = the mean of the region over all T level-0 frames.
+ * A quotient whose denominator is not above 0 is NaN in both g2 and g2_err; an empty region is NaN with n_pixels = 0.
+ * Arithmetic: a lane owns a pixel and sums its products in float32 over runs of 8 frames; everything across runs, lanes, waves
+ * and pushes is float64.  There are no atomics: every wave adds into a slot of its own, and the slots of a region are summed in
+ * wave order.  A and B are formed as S - (the level's last j frames) and S - (its first j frames) from float64 frame sums.
+ * Every sum runs in an order fixed by T, npix, the label map, m and the sequence of push lengths: the same bits from run to run,
+ * and for a region alone or among others.
+ * Calls, all stateless, DEVICE pointers throughout, asynchronous on `stream`, no host synchronisation:
+ *   scan    ORs "non-finite in some frame of frames (n, npix)" into bad[p] (npix bytes, zeroed by the caller); once per chunk.
+ *   init    builds the region-ordered pixel list (raster order within a region, regions start on a wave boundary) from labels
+ *           (npix int32 or NULL: then n_regions must be 1) and bad (or NULL), and zeroes the state.
+ *   push    consumes frames (n, npix) float32 after t0 earlier frames, 1 <= n <= max_push, any parity.  The cascade state follows
+ *           from t0: level l has received floor(t0 / 2^l) frames and holds an unpaired frame when that is odd.  Per level and
+ *           used pixel the workspace carries the last m - 1 frames (the newest of them is the unpaired frame) and, per wave,
+ *           the float64 sums.
+ *   finish  T = frames pushed; n_levels as b4d_multi_tau_lags returns it for (T, m, max_level).  g2, g2_err: (R, n_lags) float64,
+ *           mean: (R) float64, n_pixels: (R) int64.
+ *   lags    HOST helper and the one definition of the lag table: fills lags, levels, n_pairs (n_lags entries each, or NULL) and
+ *           *n_levels (or NULL), returns n_lags, or a negative error code.  max_level < 0: no cap.
+ * workspace: b4d_multi_tau_workspace_bytes(npix, n_regions, m, n_levels, max_push) bytes (0 for an unsupported shape): per level
+ * m frames of npix + 64 R floats, two scratch buffers of max_push / 2 and max_push / 4 such frames, and the per-wave sums.
+ * Limits: m in {8, 16, 32}, R <= 64, npix < 2^31, T < 2^31, at most 24 levels (B4D_ESIZE beyond).                          */
+size_t b4d_multi_tau_workspace_bytes(long long npix, int n_regions, int m, int n_levels, int max_push);
+int b4d_multi_tau_lags(long long T, int m, int max_level, long long* lags, int* levels, long long* n_pairs, int* n_levels);
+int b4d_multi_tau_scan(const float* frames, int n, long long npix, unsigned char* bad, void* stream);
+int b4d_multi_tau_init(const int* labels, const unsigned char* bad, long long npix, int n_regions, int m, int n_levels, int max_push,
+                       void* workspace, void* stream);
+int b4d_multi_tau_push(const float* frames, long long t0, int n, long long npix, int n_regions, int m, int n_levels, int max_push,
+                       void* workspace, void* stream);
+int b4d_multi_tau_finish(long long T, long long npix, int n_regions, int m, int n_levels, int max_push, void* workspace, double* g2,
+                         double* g2_err, double* mean, long long* n_pixels, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
