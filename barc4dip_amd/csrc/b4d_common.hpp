@@ -29,6 +29,7 @@ extern std::atomic<int> g_opt_track_predict;   // "track_predict_bin" 0 / 1 / 2
 extern std::atomic<int> g_opt_lanes;           // "lanes": two-lane launch groups (Lanes, b4d_fft2d.hpp); 0 = the caller's stream only
 extern std::atomic<int> g_opt_ysplit;          // "ysplit": parity-tile route of 2048-row PSD + autocorrelation; 0 = off
 extern std::atomic<int> g_opt_row16;           // "row16": 16-byte global accesses in the row passes of that route; 0 = narrow kernels
+extern std::atomic<int> g_opt_colsets;         // "colsets": column-set tiles between the forward row pass and the column pass of that route
 extern std::atomic<int> g_opt_exp;             // "exp": development A/B switch (kernel variants under test; 0 = shipped)
 
 // hipFuncAttributeMaxDynamicSharedMemorySize >= bytes for `kernel` on the CURRENT device, set once per (kernel address, device):

@@ -382,6 +382,46 @@ struct Fft3 {
             for (int s = 0; s < NS; ++s) stage3(v[s]);
         }
     }
+
+    // Stages 1 and 2 with the twiddles read from LDS, for a caller that starts set 0 while the loads of set 1 are still in flight
+    // (k_col on column-set tiles, b4d_fft2d.hpp): a twiddle fetched from memory AFTER those loads would return after them (vector
+    // memory returns in order) and the first butterfly would wait for the whole tile; LDS reads count on their own.  tab[i] = tw[i],
+    // i < N; tws[q2 * R3 + m1] = tw[R1 * m1 * q2], M values (one lane address + immediate offsets: per-lane addresses m1 * q2
+    // would live in 15 registers from the first set's stage 2 to the last one's).  Same products as stage1 / stage2, bit for bit.
+    static __device__ __forceinline__ void stage1_lds(float2 (&v)[E], int u, const float2* __restrict__ tab) {
+        static_assert(E == R1, "one stage-1 butterfly per lane");
+        butterflies<R1, 1, 1>(v);
+        __builtin_amdgcn_sched_barrier(0);   // the 30 registers of the twiddles are taken after the butterflies, not under them
+        int ug = u;   // offsets computed here, not kept from an earlier use of u * k2
+        asm volatile("" : "+v"(ug));
+#pragma unroll
+        for (int k2 = 1; k2 < R1; ++k2) v[k2] = cmul(v[k2], tab[ug * k2]);
+    }
+    static __device__ __forceinline__ void stage2_lds(float2 (&v)[E], int u, const float2* __restrict__ tws) {
+        static_assert(E == R2, "one stage-2 butterfly per lane");
+        butterflies<R2, 1, 1>(v);
+        const int m1 = u / R1;
+#pragma unroll
+        for (int q2 = 1; q2 < R2; ++q2) v[q2] = cmul(v[q2], tws[q2 * R3 + m1]);
+    }
+    // run_sets without stage 3, set by set: set s goes through stage 1, exchange 1, stage 2 and exchange 2 before set s + 1 starts
+    // (run_sets: stage 1 and exchange 1 of every set, then stage 2 and exchange 2 of every set).  Same entry / exit contract; the
+    // tables must be visible to every lane on entry.  With the twiddles out of the registers the order fits 128 VGPRs without a spill.
+    template <int NS>
+    static __device__ __forceinline__ void run_sets_staged(float2 (&v)[NS][E], int u, int ci, float2* __restrict__ lds,
+                                                           const float2* __restrict__ tws, const float2* __restrict__ tab) {
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            stage1_lds(v[s], u, tab);
+            if (s > 0) sync();
+            xchg1(v[s], u, ci, lds);
+            __builtin_amdgcn_sched_barrier(0);
+            stage2_lds(v[s], u, tws);
+            sync();
+            xchg2(v[s], u, ci, lds);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
 };
 
 }  // namespace b4d

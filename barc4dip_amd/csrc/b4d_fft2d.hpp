@@ -28,6 +28,9 @@
 //   K3 row_c2r   transform y in [0, h/2] reads row y of E and O, G(y) = E + conj(w^y) O and G(h - y) = conj(E - conj(w^y) O) ride
 //                the two-row packing; rows y, h - y and their point mirrors are written, every row once.
 //   k_nyq        unchanged (K1 still stores the plain Nyquist bins of both rows).
+// "colsets" (with "row16", nx <= 2048): between K1 and K2 a parity tile is laid out [n][e][cp][h] -- 16 bytes hold
+// rows n and n + h/2 of ONE column -- so that K2 has its first register set complete after half of its loads; K2 writes the tile back
+// in the plain form, K3 and k_nyq see no difference.
 //
 // All of them are HBM-bandwidth bound; see DESIGN.md for the byte accounting.
 #pragma once
@@ -134,7 +137,12 @@ struct RowSrc {
 // 16 bytes into the even and into the odd tile row (8 instead of 16 stores per lane, whole lines per wave instruction).  Same
 // expressions, same values bit for bit; needs a 16-byte-aligned workspace (launch_r2c).  The loads stay one dword per lane: 16-byte
 // loads, redistributed through the buffer or by quad transposes, were measured and dropped.
-template <int NX, int SEQ, bool SRC, int ITER = 1, bool YS = false, bool W16 = false>
+// CS (W16 only; "colsets" of b4d_set_option): the column-set tile layout [n][e][cp][h]: 16 bytes of a 32-column parity
+// tile hold rows n and n + ny/4 of ONE column 2 cp + e.  The SEQ transforms of a workgroup are SEQ/2 couples, pairs q and q + ny/4;
+// after every transform has written its bins to its buffer (a workgroup barrier: the partner may sit in another wave) the 2T lanes of
+// a couple split bin k of BOTH transforms, each with its own w^pair, and store 16 bytes = (q, q + ny/4) into the even and into the odd
+// tile: 4 bins and 8 stores per lane as with W16 alone, 16 consecutive lanes per 256-byte (n, e) run.  Same expressions per bin.
+template <int NX, int SEQ, bool SRC, int ITER = 1, bool YS = false, bool W16 = false, bool CS = false>
 __global__ void __launch_bounds__((NX / E16) * SEQ)
 k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __restrict__ nyq_rows,
           const float2* __restrict__ tw, int ny, int ct_w, const RowSrc* __restrict__ srcs, const float2* __restrict__ tw_y) {
@@ -145,6 +153,7 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
     static_assert(!YS || !SRC, "the ysplit pairing takes full frames");
     static_assert(!W16 || YS, "16-byte stores: parity-tile route only");
     static_assert(!W16 || G::LDS_ELEMS % 2 == 0, "16-byte accesses to each transform's buffer");
+    static_assert(!CS || (W16 && ITER == 1 && SEQ % 2 == 0), "column sets: couples of transforms, one group per workgroup");
     __shared__ __attribute__((aligned(16))) float2 lds_all[SEQ * G::LDS_ELEMS];
     const int seq = threadIdx.x / T, u = threadIdx.x % T;
     const size_t frame = blockIdx.y;
@@ -155,11 +164,17 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
         if (wb <= srcs[frame].y0 || wa >= srcs[frame].y1) return;
     }
     float2* lds = lds_all + seq * G::LDS_ELEMS;
+    // CS with ONE couple per workgroup (nx = 2048): a workgroup reads four rows ny/4 apart where the two transforms of a plain workgroup
+    // read two runs of two adjacent rows, and that alone cost the pass 7 %.  Workgroups b and b + 8 -- dealt to the
+    // same XCD one after the other -- take the adjacent couples q, q + 1 instead.  Speed only: a bijection of the grid.
+    int bx = blockIdx.x;
+    if (CS && SEQ == 2 && gridDim.x % 16 == 0) bx = (bx & ~15) + 2 * (bx & 7) + ((bx >> 3) & 1);
     float2 va[ITER][E];
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         float2(&v)[E] = va[it];
-        const int pair = (blockIdx.x * ITER + it) * SEQ + seq;
+        // CS: transforms seq and seq + SEQ/2 are a couple, pairs q and q + ny/4
+        const int pair = CS ? bx * (SEQ / 2) + seq % (SEQ / 2) + (ny / 4) * (seq / (SEQ / 2)) : (blockIdx.x * ITER + it) * SEQ + seq;
         const bool live = 2 * pair < ny;  // ragged last workgroup: idle transforms still take part in the barriers
         if (!live) {
 #pragma unroll
@@ -189,13 +204,55 @@ k_row_r2c(const float* __restrict__ in, float2* __restrict__ spec, float* __rest
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
         float2(&v)[E] = va[it];
-        const int pair = (blockIdx.x * ITER + it) * SEQ + seq;
+        const int pair = CS ? bx * (SEQ / 2) + seq % (SEQ / 2) + (ny / 4) * (seq / (SEQ / 2)) : (blockIdx.x * ITER + it) * SEQ + seq;
         const bool live = 2 * pair < ny;
         if (it > 0) fft_sync<WV>();   // the previous group's Hermitian split has read the buffer
         Fft3<G, 1, WV>::run(v, v, u, 0, lds, tw);
         fft_sync<WV>();
 #pragma unroll
         for (int j = 0; j < E; ++j) lds[u + T * j] = v[j];
+        if (CS) {
+            constexpr int H = SEQ / 2, L = 2 * T, CW = 32;   // couples per workgroup, lanes per couple, columns per parity tile
+            static_assert((NX / 2) % CW == 0 && (NX / 2) / L == 4, "four bins per lane, whole tiles");
+            const int sq = seq % H, q = bx * H + sq, m0 = u + T * (seq / H);
+            const bool both = q < ny / 4;   // a couple is live or idle as a whole
+            const float2* lp[2] = {lds_all + sq * G::LDS_ELEMS, lds_all + (sq + H) * G::LDS_ELEMS};
+            const int pr[2] = {q, q + ny / 4};
+            float2 wp2[2] = {make_float2(1.f, 0.f), make_float2(1.f, 0.f)};
+            if (both) {
+                wp2[0] = tw_y[pr[0]];
+                wp2[1] = tw_y[pr[1]];
+            }
+            __syncthreads();   // every path, idle transforms included: the partner's bins are read below
+            if (both) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int m = m0 + L * i;   // slot (tile, e, cp) of the lane: m = 32 tile + 16 e + cp
+                    const int k = (m & ~(CW - 1)) + 2 * (m & 15) + ((m >> 4) & 1);   // bin = column 2 cp + e of that tile
+                    float2 ev[2], od[2];
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const float2 z = lp[h][k], zr = lp[h][(NX - k) & (NX - 1)];
+                        float2 a = make_float2(0.5f * (z.x + zr.x), 0.5f * (z.y - zr.y));
+                        float2 b = make_float2(0.5f * (z.y + zr.y), 0.5f * (zr.x - z.x));
+                        if (k == 0) {  // DC bins are real; the (real) Nyquist bins of both rows go to the side array
+                            const float2 zn = lp[h][NX / 2];
+                            a = make_float2(z.x, 0.f);
+                            b = make_float2(z.y, 0.f);
+                            nyq_rows[frame * ny + pr[h]] = zn.x;
+                            nyq_rows[frame * ny + pr[h] + ny / 2] = zn.y;
+                        }
+                        ev[h] = cadd(a, b);
+                        od[h] = cmul(csub(a, b), wp2[h]);
+                    }
+                    // tile row n = q: 64 elements [e][cp][h], this lane's 16 bytes at 2 (16 e + cp)
+                    const size_t o = ((2 * frame * nt + (m / CW)) * (size_t)(ny / 2)) * CW + (size_t)q * (2 * CW) + 2 * (m & (CW - 1));
+                    *reinterpret_cast<f32x4*>(spec + o) = f32x4{ev[0].x, ev[0].y, ev[1].x, ev[1].y};
+                    *reinterpret_cast<f32x4*>(spec + o + (size_t)(ny / 2) * (NX / 2)) = f32x4{od[0].x, od[0].y, od[1].x, od[1].y};
+                }
+            }
+            continue;
+        }
         fft_sync<WV>();
         if (W16) {
             if (live) {
@@ -348,10 +405,18 @@ __device__ __forceinline__ void store_cols(float2* __restrict__ rowp, const floa
 }
 
 // grid (nt, batch), block ColCfg<NY>::THREADS.
-template <int NY, int MODE, int UNIT = 0, int YS = 0>
+// CS (YS only; "colsets" of b4d_set_option): the tile comes in the column-set layout [n][e][cp][h] of k_row_r2c<.., CS>: one 16-byte
+// load holds rows n and n + NY/2 of column 2 cp + e, i.e. v[e][j] and v[e][j + 8].  The eight loads of set 0 are issued by EVERY wave
+// (a workgroup barrier that leaves them in flight) ahead of the eight of set 1, so set 0 is complete after half of the tile and goes
+// through stage 1 ... exchange 2 while set 1 lands (Fft3::run_sets_staged).  For that no twiddle may queue behind set 1's loads: every
+// lane loads one entry of the 1024-point table and one of the 64 stage-2 values first of all and puts them into LDS behind the
+// exchange region before that barrier.  The tile is written back in the plain [row][column] form (every lane has read all of it by
+// then), so the inverse row pass and k_nyq do not change.  Bit-identical to CS = 0.
+template <int NY, int MODE, int UNIT = 0, int YS = 0, int CS = 0>
 __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WAVES_PER_EU)) k_col(ColArgs p) {
     using Cfg = ColCfg<NY, YS>;
     static_assert(YS == 0 || MODE == COL_PSD_AC, "parity tiles: fused PSD + autocorrelation pass only");
+    static_assert(CS == 0 || (YS && NY == 1024), "column sets: 1024-row parity tiles");
     static_assert(Cfg::NC == 2, "two columns per lane: one 16-byte load / store per row, one 8-byte PSD store");
     constexpr int NYF = YS ? 2 * NY : NY;   // rows of the frame (YS: this workgroup transforms every second ky of them)
     using G = typename Cfg::G;
@@ -388,27 +453,56 @@ __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WA
         ry0 = p.srcs[fr].y0;
         ry1 = p.srcs[fr].y1;
     }
+    if constexpr (CS != 0) {
+        static_assert(NC == 2 && T == 64 && Cfg::THREADS == NY, "two sets of eight 16-byte loads; one entry of the stage-1 table per lane");
+        float2* tws = lds + (size_t)G::LDS_ELEMS * CPT;   // stage-2 twiddles: entry q2 R3 + m1 = tw[R1 m1 q2]
+        float2* tab = tws + G::M;                         // the whole table tw[i], i < NY, for stage 1
+        const float2 t1 = p.tw[threadIdx.x];
+        const float2 t2 = p.tw[G::R1 * ((threadIdx.x % G::R3) * (threadIdx.x / G::R3 % G::R2))];
+        const unsigned toffc = ((unsigned)u * 2 * CT + 2 * cp) * 8u;   // byte offset of (row u, e = 0, cp, h = 0)
 #pragma unroll
-    for (int h = 0; h < NC / 2; ++h) {
+        for (int s = 0; s < NC; ++s) {
 #pragma unroll
-        for (int j = 0; j < E; ++j) {
-            if (MODE == COL_FORWARD) {   // clamped row + select: the load stays unconditional (no branch per load), rows outside the
-                                         // ROI re-read a ROI row that other lanes fetch anyway
-                const int ky = u + T * j, kc = min(max(ky, ry0), ry1 - 1);
-                float4 q = *reinterpret_cast<const float4*>(tile + (size_t)kc * CT + NC * cp + 2 * h);
-                if (ky < ry0 || ky >= ry1) q = make_float4(0.f, 0.f, 0.f, 0.f);
-                v[2 * h][j] = make_float2(q.x, q.y);
-                v[2 * h + 1][j] = make_float2(q.z, q.w);
-            } else {
-                const f32x4 q = *at_bytes<f32x4>(sgpr_base(tile + (size_t)(T * j * CT) + 2 * h), toff * 8u);
-                v[2 * h][j] = make_float2(q.x, q.y);
-                v[2 * h + 1][j] = make_float2(q.z, q.w);
+            for (int j = 0; j < E / 2; ++j) {
+                const f32x4 q = *at_bytes<f32x4>(sgpr_base(tile + (size_t)(T * j * 2 * CT + s * CT)), toffc);
+                v[s][j] = make_float2(q.x, q.y);
+                v[s][j + E / 2] = make_float2(q.z, q.w);
+            }
+            if (s == 0) {   // the memory pipe sees set 0 of all waves ahead of any load of set 1; the loads stay in flight across it
+                if (threadIdx.x < G::M) tws[threadIdx.x] = t2;
+                tab[threadIdx.x] = t1;   // waits for the two oldest loads of the queue only
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // set 1's loads are issued here, not where the scheduler finds room for their registers
+    } else {
+#pragma unroll
+        for (int h = 0; h < NC / 2; ++h) {
+#pragma unroll
+            for (int j = 0; j < E; ++j) {
+                if (MODE == COL_FORWARD) {   // clamped row + select: the load stays unconditional (no branch per load), rows outside
+                                             // the ROI re-read a ROI row that other lanes fetch anyway
+                    const int ky = u + T * j, kc = min(max(ky, ry0), ry1 - 1);
+                    float4 q = *reinterpret_cast<const float4*>(tile + (size_t)kc * CT + NC * cp + 2 * h);
+                    if (ky < ry0 || ky >= ry1) q = make_float4(0.f, 0.f, 0.f, 0.f);
+                    v[2 * h][j] = make_float2(q.x, q.y);
+                    v[2 * h + 1][j] = make_float2(q.z, q.w);
+                } else {
+                    const f32x4 q = *at_bytes<f32x4>(sgpr_base(tile + (size_t)(T * j * CT) + 2 * h), toff * 8u);
+                    v[2 * h][j] = make_float2(q.x, q.y);
+                    v[2 * h + 1][j] = make_float2(q.z, q.w);
+                }
             }
         }
     }
     B4D_DRAIN();
     B4D_STAMP(1);
-    Fft3<G, 1>::template run_sets<NC, MODE != COL_PSD_AC>(v, u, cp, lds, p.tw);
+    if constexpr (CS != 0)
+        Fft3<G, 1>::template run_sets_staged<NC>(v, u, cp, lds, lds + (size_t)G::LDS_ELEMS * CPT, lds + (size_t)G::LDS_ELEMS * CPT + G::M);
+    else
+        Fft3<G, 1>::template run_sets<NC, MODE != COL_PSD_AC>(v, u, cp, lds, p.tw);
     B4D_STAMP(2);
     // v[c][j] = F[ky = u + T j][kx0 + c]   (COL_PSD_AC: after the stage-3 butterflies done below)
     const int kx0 = ctx * CT + NC * cp;
@@ -1063,24 +1157,30 @@ struct Route {
     int ct_w;              // complex columns per tile
     const float2* tw_col;  // twiddles of the transform the column pass runs: ny/2 points on parity tiles, ny points otherwise
     int row16;             // parity route: the row passes may move 16 bytes per lane ("row16"); their launchers check the alignment
+    int colsets;           // parity route with row16, nx <= 2048: column-set tiles between the forward row pass and the column pass
+                           // ("colsets"); BOTH launchers check the workspace's alignment (colsets_of)
 };
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+// the one decision the forward row pass and the column pass must share: which layout the tiles between them have
+static inline int colsets_of(const Route& rt, const void* spec) { return rt.parity && rt.row16 && aligned16(spec) ? rt.colsets : 0; }
 
 // Launchers: one per pass, the route (YS: parity tiles) a template argument.  A dispatcher instantiates every kernel it names in the
 // including unit: the plain-route ones (dispatch_r2c, dispatch_c2r) are ordinary functions, the *_route templates let the one unit
 // that runs the parity-tile kernels of a pass build them.
 #if B4D_UNIT_PASSES & B4D_PASS_COL
 // grid: one workgroup per tile; YS: 1024-point parity tiles of 2048-row frames, a.tw / a.tw_inv = 1024-point twiddles
-template <int NY, int MODE, int YS = 0>
+// CS: column-set tiles (k_col); the two twiddle tables (8.5 KiB) sit behind the exchange region
+template <int NY, int MODE, int YS = 0, int CS = 0>
 static int launch_col(const ColArgs& a, int batch, hipStream_t st) {
     using Cfg = ColCfg<NY, YS>;
+    constexpr size_t LDS_BYTES = Cfg::LDS_BYTES + (CS ? sizeof(float2) * (Cfg::G::M + NY) : 0);
     if ((a.nx / 2) % Cfg::CT) return fail(B4D_ESIZE, "column pass: nx / 2 is no multiple of the tile width");
     {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<NY, MODE, B4D_UNIT_TAG, YS>), Cfg::LDS_BYTES);
+        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<NY, MODE, B4D_UNIT_TAG, YS, CS>), LDS_BYTES);
         if (rc_lds) return rc_lds;
     }
-    hipLaunchKernelGGL((k_col<NY, MODE, B4D_UNIT_TAG, YS>), dim3((YS ? 2 : 1) * ((a.nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
-                       Cfg::LDS_BYTES, st, a);
+    hipLaunchKernelGGL((k_col<NY, MODE, B4D_UNIT_TAG, YS, CS>), dim3((YS ? 2 : 1) * ((a.nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
+                       LDS_BYTES, st, a);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
@@ -1117,7 +1217,7 @@ static int dispatch_nyq(const b4d_plan* pl, NyqArgs a, int items, hipStream_t st
 // YS: rows p and p + ny/2 per transform, parity tile sets (full frames only); otherwise srcs != null selects ROI / z-score sources
 template <int NX, bool YS>
 static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* nyq_rows, const RowSrc* srcs, int ct_w, int batch,
-                      hipStream_t st, int row16) {
+                      hipStream_t st, int row16, int colsets) {
     constexpr int SEQ = row_seq(NX);
     constexpr int ITER = NX >= 1024 ? B4D_K1_ITER : 1;   // groups of row pairs per workgroup, full frames only
     const dim3 block((NX / E16) * SEQ), grid((pl->ny / 2 + SEQ - 1) / SEQ, batch),
@@ -1125,6 +1225,17 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
     if (YS && srcs) return fail(B4D_EINVAL, "parity tiles take full frames");
     if constexpr (YS) {
         // 16-byte stores need a 16-byte-aligned workspace (the loads are dwords: the frames may sit anywhere); the narrow kernel otherwise
+        if constexpr (SEQ % 2 == 0) {
+            if (colsets && row16 && aligned16(spec)) {   // couples of transforms: one group of SEQ pairs per workgroup
+                if (ct_w != 32 || (pl->ny / 2) % SEQ) return fail(B4D_ESIZE, "column-set tiles: 32 columns, whole workgroups");
+                hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, 1, true, true, true>), grid, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny,
+                                   ct_w, srcs, pl->tw_y);
+                B4D_HIP(hipGetLastError());
+                return B4D_OK;
+            }
+        } else if (colsets) {
+            return fail(B4D_ESIZE, "column-set tiles need two transforms per workgroup");
+        }
         if (row16 && aligned16(spec))
             hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny,
                                ct_w, srcs, pl->tw_y);
@@ -1142,8 +1253,8 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
 }
 template <bool YS>
 static int dispatch_r2c_route(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows,
-                              const RowSrc* srcs, int ct_w, int row16 = 0) {
-#define B4D_CALL(N) launch_r2c<N, YS>(pl, in, spec, nyq_rows, srcs, ct_w, batch, st, row16)
+                              const RowSrc* srcs, int ct_w, int row16 = 0, int colsets = 0) {
+#define B4D_CALL(N) launch_r2c<N, YS>(pl, in, spec, nyq_rows, srcs, ct_w, batch, st, row16, colsets)
     B4D_SIZE_SWITCH(pl->nx, B4D_CALL)
 #undef B4D_CALL
     return fail(B4D_ESIZE, "unsupported nx");

@@ -60,6 +60,8 @@ std::atomic<int> g_opt_lanes{1};
 std::atomic<int> g_opt_exp{0};
 std::atomic<int> g_opt_ysplit{1};   // "ysplit": 2048-row PSD + autocorrelation through parity tiles (b4d_fft2d.hpp); 0 = full-column tiles
 std::atomic<int> g_opt_row16{1};   // "row16": 16-byte global accesses in the row passes of the parity-tile route; 0 = the narrow kernels
+std::atomic<int> g_opt_colsets{1};   // "colsets": column-set tiles between the forward row pass and the column pass of that route (needs
+                                     // "row16"): set 0 of the column pass is transformed under set 1's loads; 0 = plain tiles
 // b4d_spectrum.hip
 int spectrum_rows_last(const b4d_plan* pl, float2* spec, const float* frames, int batch, float2* out, hipStream_t st);
 }  // namespace b4d
@@ -118,7 +120,7 @@ int b4d_set_option(const char* name, int value) {
         int lo, hi;
     };
     const Opt opts[] = {{"track_predict_bin", &g_opt_track_predict, 0, 2}, {"lanes", &g_opt_lanes, 0, 1}, {"exp", &g_opt_exp, 0, 255},
-                        {"ysplit", &g_opt_ysplit, 0, 1}, {"row16", &g_opt_row16, 0, 1}};
+                        {"ysplit", &g_opt_ysplit, 0, 1}, {"row16", &g_opt_row16, 0, 1}, {"colsets", &g_opt_colsets, 0, 1}};
     for (const Opt& o : opts)
         if (!strcmp(name, o.name)) {
             if (value < o.lo || value > o.hi)
@@ -243,7 +245,7 @@ extern "C" void b4d_debug_set_diag(void* buf) { g_diag = static_cast<unsigned lo
 // Forward row pass of the PSD + autocorrelation pipeline on the call's route: this unit's counterpart of col_psd_ac_pass and
 // row_out_pass (b4d_passes.hpp), and the only place that builds the parity-tile k_row_r2c.
 static int row_in_pass(const b4d_plan* pl, const float* in, int batch, hipStream_t st, float2* spec, float* nyq_rows, const Route& rt) {
-    return rt.parity ? dispatch_r2c_route<true>(pl, in, batch, st, spec, nyq_rows, nullptr, rt.ct_w, rt.row16)
+    return rt.parity ? dispatch_r2c_route<true>(pl, in, batch, st, spec, nyq_rows, nullptr, rt.ct_w, rt.row16, colsets_of(rt, spec))
                      : dispatch_r2c(pl, in, batch, st, spec, nyq_rows);
 }
 
@@ -262,7 +264,9 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
     // one route per call, chosen by the frame shape alone (never by batch, chunk or lanes): 2048-row frames take the parity-tile
     // route, where the row passes do one radix-2 stage of the column transform
     const bool parity = pl->ny == 2048 && pl->tw_yh && g_opt_ysplit.load();
-    const Route rt = parity ? Route{true, ColCfg<1024, 1>::CT, pl->tw_yh, g_opt_row16.load()} : Route{false, pl->ct_w, pl->tw_y, 0};
+    // column-set tiles need two row transforms per workgroup of the forward row pass: every nx but 4096
+    const Route rt = parity ? Route{true, ColCfg<1024, 1>::CT, pl->tw_yh, g_opt_row16.load(), pl->nx <= 2048 ? g_opt_colsets.load() : 0}
+                            : Route{false, pl->ct_w, pl->tw_y, 0, 0};
     std::vector<hipEvent_t> ev;
     auto mark = [&]() -> int {
         if (!kernel_ms) return B4D_OK;

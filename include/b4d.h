@@ -63,6 +63,11 @@ const char* b4d_last_error(void);
  *                        allow it: the workspace, and for the inverse pass the caller's `autocorr`, must be 16-byte aligned --
  *                        checked per call, the 4- and 8-byte kernels run otherwise; 0 = the 4- and 8-byte kernels always.  Only
  *                        which lane moves which element differs: results are bit-identical.
+ *   "colsets"            0 / 1 (default 1): 1 = on the "ysplit" route with "row16" (16-byte-aligned workspace, nx <= 2048) the forward
+ *                        row pass hands the column pass "column-set" tiles: every 16 bytes hold rows n and n + 512 of ONE column, so
+ *                        the column pass has the first of its two register sets complete after half of its loads and transforms it
+ *                        while the other half lands; 0 = the plain [row][column] tiles.  Only the placement of the data in the
+ *                        workspace and the order of independent work differ: results are bit-identical.
  *   "exp"                0 .. 255 (default 0): development switch for A/B runs of kernel variants under test in ONE process
  *                        (tools/dev_*.py); a shipped library has no reader of it.
  * Values outside an option's range and unknown names return B4D_EINVAL; the options are atomics, read once per entry-point call. */
