@@ -1,9 +1,12 @@
-"""GPU drop-in for ``barc4dip.preprocessing`` (deconvolve_psf, flat_field_correction) and distortion correction."""
+"""GPU drop-in for ``barc4dip.preprocessing`` (deconvolve_psf, flat_field_correction), distortion correction and spatial
+rank filters with outlier repair."""
 from __future__ import annotations
 
 from . import distortion
 from .distortion import correct_distortion, remove_distortion
 from .filters import deconvolve_psf
 from .normalize import flat_field_correction
+from .rank import median_filter, percentile_filter, rank_filter, remove_outliers
 
-__all__ = ["deconvolve_psf", "flat_field_correction", "distortion", "correct_distortion", "remove_distortion"]
+__all__ = ["deconvolve_psf", "flat_field_correction", "distortion", "correct_distortion", "remove_distortion",
+           "median_filter", "rank_filter", "percentile_filter", "remove_outliers"]

@@ -628,6 +628,37 @@ int b4d_multi_tau_push(const float* frames, long long t0, int n, long long npix,
 int b4d_multi_tau_finish(long long T, long long npix, int n_regions, int m, int n_levels, int max_push, void* workspace, double* g2,
                          double* g2_err, double* mean, long long* n_pixels, void* stream);
 
+/* Spatial rank filters (scipy.ndimage.median_filter / rank_filter / percentile_filter on every frame of (batch, ny, nx) float32),
+ * the range-only variant behind utils/range.py:14-86, fused outlier repair, and the uint16 scaling of utils/dtype.py:15-53.
+ * A rank filter is a selection: on finite input the output equals SciPy's bit for bit.  NaN sorts above +Inf and -0 below +0
+ * (np.sort's order; SciPy leaves NaN unspecified).  DEVICE pointers throughout, asynchronous on `stream`, no synchronisation.
+ * b4d_rank_filter: out[t, y, x] = the rank-th smallest (0-based) of the size_y x size_x window placed as SciPy places it (offsets
+ *   -(size / 2) .. size - 1 - size / 2 per axis), 1 <= size <= 15, 0 <= rank < size_y * size_x.
+ *   mode: the codes of b4d_warp_* -- 0 "nearest", 1 "reflect", 2 "mirror", 3 "constant" (cval) -- and 4 "wrap", with SciPy's
+ *   meanings, for any overhang (a window larger than the frame reflects or wraps repeatedly).
+ *   flags bit 0: take the general route (32 counting passes per output) also where the register route applies (the median of
+ *   3 x 3, 5 x 5, 7 x 7); both are exact, so the outputs are identical.
+ *   out: (batch, ny, nx) or NULL.  minmax: (batch, 2) float32 {nanmin, nanmax} of every filtered frame, NaN for a frame whose
+ *   filtered values are all NaN, or NULL; with out == NULL nothing but minmax is written (4 B per pixel of traffic).  The
+ *   reduction is integer min / max on ordered keys: deterministic.
+ * b4d_despeckle: out = median of the size x size window (size 3, 5 or 7) where the centre pixel x is an outlier, else x.  With
+ *   med the window median and d = x - med, in float32 and in this operation order:
+ *     scale_kind 0 "absolute": |d| > threshold
+ *     scale_kind 1 "mad"     : |d| > threshold * max(1.4826f * mad, min_scale), mad = median of |w_i - med| over the same window
+ *     scale_kind 2 "poisson" : d * d > (threshold * threshold) * max(med, min_scale), the square formed in float32 on the host
+ *   (max as np.maximum: NaN stays NaN).  polarity 0 both, 1 hot (and d > 0), 2 dead (and d < 0); a non-finite centre pixel is
+ *   always an outlier.  mask: (batch, ny, nx) bytes, 1 = replaced, or NULL.  counts: (batch) int64 replaced pixels per frame
+ *   (integer adds), or NULL.  threshold >= 0, min_scale >= 0.
+ * b4d_scale_to_u16: out[i] = (uint16) clip((in[i] - vmin) * inv, 0, 65535), truncated: the subtraction in float32; the product
+ *   in float64 rounded once to float32 when mul_f64 (NumPy's float32 array times a float64 scalar), else in float32 by
+ *   (float) inv.  NaN -> 0.
+ * B4D_EINVAL: sizes, rank, mode or kinds out of range, batch < 1, overlapping buffers (in == out), no output at all.        */
+int b4d_rank_filter(const float* in, int batch, int ny, int nx, int size_y, int size_x, int rank, int mode, float cval, int flags,
+                    float* out, float* minmax, void* stream);
+int b4d_despeckle(const float* in, int batch, int ny, int nx, int size, int scale_kind, float threshold, float min_scale, int polarity,
+                  int mode, float cval, float* out, unsigned char* mask, long long* counts, void* stream);
+int b4d_scale_to_u16(const float* in, size_t n, float vmin, double inv, int mul_f64, unsigned short* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
