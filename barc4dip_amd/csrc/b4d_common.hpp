@@ -26,7 +26,7 @@ std::recursive_mutex& scratch_mutex();
 
 // b4d_set_option switches (defined next to it, b4d_kernels.hip): routes only, never results; read once per entry-point call
 extern std::atomic<int> g_opt_track_predict;   // "track_predict_bin" 0 / 1 / 2
-extern std::atomic<int> g_opt_lanes;           // "lanes": two-lane launch groups (Lanes, b4d_fft2d.hpp); 0 = the caller's stream only
+extern std::atomic<int> g_opt_lanes;           // "lanes": two-lane launch groups (Lanes, b4d_lanes.hpp); 0 = the caller's stream only
 extern std::atomic<int> g_opt_ysplit;          // "ysplit": parity-tile route of 2048-row PSD + autocorrelation; 0 = off
 extern std::atomic<int> g_opt_row16;           // "row16": 16-byte global accesses in the row passes of that route; 0 = narrow kernels
 extern std::atomic<int> g_opt_colsets;         // "colsets": column-set tiles between the forward row pass and the column pass of that route
@@ -47,5 +47,16 @@ int lane_stream(int idx, hipStream_t* out);
         if (e__ != hipSuccess)                                                             \
             return ::b4d::fail(B4D_EHIP, std::string(#call) + ": " + hipGetErrorString(e__)); \
     } while (0)
+
+// The launch of every kernel that takes dynamic LDS (and of any other): the dynamic-LDS attribute where lds != 0
+// (ensure_dynamic_lds), the launch, and its one error check.  The arguments are converted to the kernel's own parameter types.
+template <class... P, class... A>
+static int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
+    if (lds)
+        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    B4D_HIP(hipGetLastError());
+    return B4D_OK;
+}
 
 }  // namespace b4d

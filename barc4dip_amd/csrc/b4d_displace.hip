@@ -46,24 +46,6 @@ struct DispArgs {
     int* peak_ij;            // (npairs, gy, gx, 2) or null
 };
 
-// sum of 4 doubles over the workgroup (<= 4 waves), result in every lane
-__device__ inline void dm_block_sum4(double (&v)[4], double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-        if (lane == 0) red[wave * 4 + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = 0.0;
-        for (int i = 0; i < nwave; ++i) v[k] += red[i * 4 + k];
-    }
-    __syncthreads();
-}
-
 __device__ __forceinline__ float dm_readlane(float v, int lane) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
 }
@@ -115,7 +97,8 @@ __global__ void __launch_bounds__(DM_THREADS) k_displace(DispArgs a) {
             s[2] += d;
             s[3] += d * d;
         }
-        dm_block_sum4(s, red);
+        block_sum_all(s, red, nthr >> 6);
+        __syncthreads();   // red is written again below
         const double tm = s[0] / nt, bm = s[2] / (bh * bw);
         const double tsd = sqrt(fmax(s[1] / nt - tm * tm, 0.0)), bsd = sqrt(fmax(s[3] / (bh * bw) - bm * bm, 0.0));
         s[0] = t0 + tm;
@@ -132,7 +115,8 @@ __global__ void __launch_bounds__(DM_THREADS) k_displace(DispArgs a) {
         q[0] += z;
         q[1] += (double)z * z;
     }
-    dm_block_sum4(q, red);
+    block_sum_all(q, red, nthr >> 6);
+    __syncthreads();
     const double tssd = fmax(q[1] - q[0] * q[0] / nt, 0.0);   // sum (tz - mean tz)^2
     // the numerator's template is tz - f32(mean tz): mean tz is ~ulp(mean) / std, 3e-6 for 30 000 counts at 1 % contrast, and
     // would otherwise enter as (window sum of the box) x (mean tz) -- the oracle's num = xc - s1 * tmean removes it exactly
@@ -239,21 +223,7 @@ __global__ void __launch_bounds__(DM_THREADS) k_displace(DispArgs a) {
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int k = tid; k < nm; k += nthr) argmax_merge(bv, bi, M[k], k);
-    // (block_argmax of b4d_peak.hpp, kept inline: through the helper this kernel's instructions come out different)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_down(bv, o, 64);
-        const int oi = __shfl_down(bi, o, 64);
-        argmax_merge(bv, bi, ov, oi);
-    }
-    if (lane == 0) {
-        sv[tid >> 6] = bv;
-        si[tid >> 6] = bi;
-    }
-    __syncthreads();
-    bv = sv[0];
-    bi = si[0];
-    for (int k = 1; k < (nthr >> 6); ++k) argmax_merge(bv, bi, sv[k], si[k]);
+    block_argmax(bv, bi, sv, si, nthr >> 6);
     if (bi == 0x7fffffff) bi = 0;   // all-NaN map: np.argmax would name the first NaN
     const int mi = bi / mw, mj = bi % mw;
     if (tid < 9) {
@@ -301,13 +271,9 @@ static int launch_displace(DispArgs a, int npairs, hipStream_t st) {
     size_t lds = 0;
     int rc = plan_bands(a, RX, attr.sharedSizeBytes, &lds);
     if (rc) return rc;
-    rc = ensure_dynamic_lds(kern, lds);
-    if (rc) return rc;
     const int ntask = (2 * a.sy + 1) * a.nch;
     const int threads = std::min(DM_THREADS, std::max(64, (ntask + 63) / 64 * 64));
-    hipLaunchKernelGGL(k_displace<RX>, dim3(a.gx, a.gy, npairs), dim3(threads), lds, st, a);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return launch(k_displace<RX>, dim3(a.gx, a.gy, npairs), dim3(threads), lds, st, a);
 }
 
 }  // namespace b4d

@@ -22,19 +22,13 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
 constexpr int NB = 32;  // subspace width
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-template <typename T>
-__device__ __forceinline__ T wsum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
 
 // ---- 1. normalisation: part[b][blk] = {sum x, sum x^2, n_nonfinite}; grid (nblk, batch), block 1024
 __global__ void __launch_bounds__(1024) k_sta2_sums(const float* __restrict__ x, size_t npix, double* __restrict__ part) {
@@ -50,9 +44,9 @@ __global__ void __launch_bounds__(1024) k_sta2_sums(const float* __restrict__ x,
             bad += 1;
         }
     }
-    s = wsum(s);
-    q = wsum(q);
-    bad = wsum(bad);
+    s = wave_sum(s);
+    q = wave_sum(q);
+    bad = wave_sum(bad);
     if ((threadIdx.x & 63) == 0) {
         sh[(threadIdx.x >> 6) * 3] = s;
         sh[(threadIdx.x >> 6) * 3 + 1] = q;
@@ -542,9 +536,7 @@ extern "C" int b4d_sta2_eigenvalues(const float* frames, int batch, int ny, int 
         hipLaunchKernelGGL(k_gram_mfma, dim3(1, 1, batch), dim3(256), 0, st, g);
         B4D_HIP(hipMemsetAsync(evd, 0, sizeof(double) * 8 * batch, st));
         const size_t lds = sizeof(double) * 2 * JS * (JS + 1);
-        if (int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_jacobi_small), lds)) return rc_lds;
-        hipLaunchKernelGGL(k_jacobi_small, dim3(batch), dim3(1024), lds, st, G, m, evd);
-        B4D_HIP(hipGetLastError());
+        if (const int rc = launch(k_jacobi_small, dim3(batch), dim3(1024), lds, st, G, m, evd)) return rc;
         std::vector<double> cur((size_t)batch * 8), hstat((size_t)3 * batch);
         B4D_HIP(hipMemcpyAsync(cur.data(), evd, sizeof(double) * cur.size(), hipMemcpyDeviceToHost, st));
         B4D_HIP(hipMemcpyAsync(hstat.data(), stat, sizeof(double) * hstat.size(), hipMemcpyDeviceToHost, st));

@@ -46,6 +46,7 @@
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
 #include "b4d_fft.hpp"
+#include "b4d_lanes.hpp"
 #include "b4d_peak.hpp"
 
 // Translation units that build a kernel with their own compiler flags (b4d_passes.hpp) define B4D_UNIT_TAG before including
@@ -754,6 +755,7 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
         float bv = -1.0f;
         int bi = 0x7fffffff;
         for (int i = threadIdx.x; i < p.nblk; i += T * SEQ) argmax_merge(bv, bi, p.part_val[frame * p.nblk + i], p.part_idx[frame * p.nblk + i]);
+        // (wave_argmax of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_down(bv, o, 64);
@@ -970,6 +972,7 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
             bi = (ls < E ? ra : rb) * NX + u + T * (ls % E);
         }
     }
+    // (wave_argmax of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float ov = __shfl_down(bv, o, 64);
@@ -994,6 +997,7 @@ __global__ void __launch_bounds__((NX / E16) * SEQ) k_row_c2r(RowOutArgs p) {
         // counts of the magnitudes below / inside the expected median bin and the bin's elements themselves: lane counts,
         // a workgroup scan, THREE global atomics per workgroup (no per-element atomics, no second read of the map)
         constexpr int NW = (T * SEQ + 63) / 64;
+        // (wave_scan_inclusive and wave_sum of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
         unsigned incl = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1073,30 +1077,7 @@ struct b4d_plan {
     // both sides have in-register three-radix kernels (b4d_wiener_mr.hip): the transform-based entry points take those passes,
     // whatever the size class (228-px aggregator tiles as well as 2560 x 2160 frames); tw_x / tw_y are built for it
     bool wmr = false;
-    // second stream of the two-lane drivers (Lanes below; the library's shared lane_stream(0); fork / join by this plan's events)
-    hipStream_t aux = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-};
-
-// Two-lane launch groups (b4d_kernels.hip).  A multi-pass transform whose intermediate is written and read once runs faster in
-// groups whose workspace is about 64 MiB -- it stays in the 256-MB memory-side cache -- and with the groups dealt alternately to
-// the caller's stream and a second one, so that the passes of one group run under those of the other (no drained chip between
-// two launches, transform phases of one kernel under the memory phases of another).  Measured, frames/s (tools/dev_fft2d_chunk.py,
-// tools/dev_pipe_chunk.py): fft2d 2048^2 61.7 k in 64-frame groups, 61.8 k in 4-frame groups, 66.5-67.7 k in 4-frame groups on two
-// lanes; 1024^2 268 -> 277 k; 2160 x 2560 28.0 -> 31.4 k; psd + autocorr 2160 x 2560 20.0 -> 22.4 k, 1080 x 1920 55 -> 62.8 k,
-// 228^2 1.72 -> 1.91 M.  (The power-of-two psd + autocorr pipeline gains 1 % at 2048^2 and keeps its single large groups.)
-struct Lanes {
-    b4d_plan* pl = nullptr;
-    hipStream_t st = nullptr;
-    bool two = false;
-    int sub = 1;   // frames per group; lane l works in slot l of the workspaces (slot stride: `sub` frames)
-    // inter_bytes: intermediate bytes per frame; two lanes need 2 * sub <= chunk and groups of at least min_group_bytes of input
-    // (below that the launches themselves are what a group costs: 256^2 frames in two lanes of 64, 2.3 against 2.9 M frames/s)
-    int open(b4d_plan* p, hipStream_t s, int batch, size_t inter_bytes, size_t frame_bytes, bool allow_two, size_t min_group_bytes);
-    int fork(b4d_plan* p, hipStream_t s, bool want_two);   // the stream part alone (group sizes are the caller's)
-    hipStream_t stream(int g) const { return two && (g & 1) ? pl->aux : st; }
-    int slot(int g) const { return two ? (g & 1) : 0; }
-    int close();   // joins the second lane into the caller's stream
+    LaneSync lanes;            // second stream and fork / join events of the two-lane drivers (b4d_lanes.hpp)
 };
 
 // b4d_general.hip
@@ -1175,14 +1156,8 @@ static int launch_col(const ColArgs& a, int batch, hipStream_t st) {
     using Cfg = ColCfg<NY, YS>;
     constexpr size_t LDS_BYTES = Cfg::LDS_BYTES + (CS ? sizeof(float2) * (Cfg::G::M + NY) : 0);
     if ((a.nx / 2) % Cfg::CT) return fail(B4D_ESIZE, "column pass: nx / 2 is no multiple of the tile width");
-    {
-        const int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(&k_col<NY, MODE, B4D_UNIT_TAG, YS, CS>), LDS_BYTES);
-        if (rc_lds) return rc_lds;
-    }
-    hipLaunchKernelGGL((k_col<NY, MODE, B4D_UNIT_TAG, YS, CS>), dim3((YS ? 2 : 1) * ((a.nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS),
-                       LDS_BYTES, st, a);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return launch(k_col<NY, MODE, B4D_UNIT_TAG, YS, CS>, dim3((YS ? 2 : 1) * ((a.nx / 2) / Cfg::CT), batch), dim3(Cfg::THREADS), LDS_BYTES,
+                  st, a);
 }
 template <int MODE>
 static int dispatch_col(const b4d_plan* pl, const ColArgs& a, int batch, hipStream_t st) {

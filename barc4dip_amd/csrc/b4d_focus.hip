@@ -40,6 +40,7 @@ __global__ void __launch_bounds__(64) k_focus_put(FocusZPack p, int count, doubl
 __device__ __forceinline__ bool focus_valid(float e, float a) { return isfinite(e) && isfinite(a) && a > 0.f; }
 
 // fixed-order sum over the 256 lanes of a workgroup; the result is valid in lane 0
+// (not block_sum of b4d_reduce.hpp: an LDS tree over all 256 lanes, another order of additions)
 __device__ __forceinline__ double focus_block_sum(double v, double* sh) {
     __syncthreads();
     sh[threadIdx.x] = v;
@@ -158,14 +159,6 @@ struct SpotArgs {
     int Py, Px, p0, cy, cx, nbands;
 };
 
-// greater value first, then the smaller index; a NaN never wins
-__device__ __forceinline__ void focus_peak_merge(double& bv, int& bi, double ov, int oi) {
-    if (ov > bv || (ov == bv && oi < bi)) {
-        bv = ov;
-        bi = oi;
-    }
-}
-
 // grid (nbands, pairs), block 256 = (256 >> LSH) rows x (1 << LSH) lanes; a lane owns the column pairs 2 (tx + m lx), m < NM.
 // The lane split is a template argument so that the row loop has a compile-time trip count: it is unrolled four rows deep, because
 // the row reduction is a chain of six dependent cross-lane steps that would otherwise bound the loop.
@@ -225,8 +218,8 @@ __global__ void __launch_bounds__(256) k_focus_spot(SpotArgs a) {
                 rs += i1;
                 rq = fma(i0, (double)q0, rq);
                 rq = fma(i1, (double)q1, rq);
-                focus_peak_merge(bv, bi, i0, sr * Px + q0 + Px / 2);
-                if (two) focus_peak_merge(bv, bi, i1, sr * Px + q1 + Px / 2);
+                argmax_merge(bv, bi, i0, sr * Px + q0 + Px / 2);
+                if (two) argmax_merge(bv, bi, i1, sr * Px + q1 + Px / 2);
                 if (rowcrop) {
                     const int x0 = q0 + a.cx / 2, x1 = q1 + a.cx / 2;
                     if (x0 >= 0 && x0 < a.cx) crop[(size_t)yy * a.cx + x0] = (float)i0;
@@ -234,6 +227,7 @@ __global__ void __launch_bounds__(256) k_focus_spot(SpotArgs a) {
                 }
             }
         }
+        // (not wave_sum_all of b4d_reduce.hpp: groups of gw <= 64 lanes, one row each)
 #pragma unroll
         for (int o = gw >> 1; o > 0; o >>= 1) {
             rs += __shfl_xor(rs, o, 64);
@@ -257,12 +251,7 @@ __global__ void __launch_bounds__(256) k_focus_spot(SpotArgs a) {
         cbuf[ty * 2 * lx + 2 * tx] = cs[0][0];
         cbuf[ty * 2 * lx + 2 * tx + 1] = cs[0][1];
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        focus_peak_merge(bv, bi, ov, oi);
-    }
+    wave_argmax_all(bv, bi);
     if ((threadIdx.x & 63) == 0) {
         pv[threadIdx.x >> 6] = bv;
         pi[threadIdx.x >> 6] = bi;
@@ -284,7 +273,7 @@ __global__ void __launch_bounds__(256) k_focus_spot(SpotArgs a) {
         a.rowq[(size_t)pair * Py + r0 + threadIdx.x] = q;
     }
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) focus_peak_merge(bv, bi, pv[w], pi[w]);
+        for (int w = 1; w < 4; ++w) argmax_merge(bv, bi, pv[w], pi[w]);
         a.peakv[(size_t)pair * a.nbands + blockIdx.x] = bv;
         a.peaki[(size_t)pair * a.nbands + blockIdx.x] = bi;
     }
@@ -348,13 +337,8 @@ __global__ void __launch_bounds__(256) k_focus_fin(FinArgs a) {
     }
     double bv = -1.0;
     int bi = INT_MAX;
-    for (int b = threadIdx.x; b < a.nbands; b += 256) focus_peak_merge(bv, bi, a.peakv[(size_t)pair * a.nbands + b], a.peaki[(size_t)pair * a.nbands + b]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        focus_peak_merge(bv, bi, ov, oi);
-    }
+    for (int b = threadIdx.x; b < a.nbands; b += 256) argmax_merge(bv, bi, a.peakv[(size_t)pair * a.nbands + b], a.peaki[(size_t)pair * a.nbands + b]);
+    wave_argmax_all(bv, bi);
     if ((threadIdx.x & 63) == 0) {
         pv[threadIdx.x >> 6] = bv;
         pi[threadIdx.x >> 6] = bi;
@@ -363,7 +347,7 @@ __global__ void __launch_bounds__(256) k_focus_fin(FinArgs a) {
     spp = focus_block_sum(spp, sh);
     spq = focus_block_sum(spq, sh);
     if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; ++w) focus_peak_merge(bv, bi, pv[w], pi[w]);
+        for (int w = 1; w < 4; ++w) argmax_merge(bv, bi, pv[w], pi[w]);
         const double nan = __longlong_as_double(0x7ff8000000000000LL);
         const bool found = bi != INT_MAX;
         s[1] = found ? bv : nan;

@@ -16,6 +16,7 @@
 #include <string>
 
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -159,14 +160,11 @@ __global__ void __launch_bounds__(FR_THREADS) k_fr_demod(const float* __restrict
                     si[k] += e.x * ci + e.y * cr;
                 }
             }
+            s0 = wave_sum(s0);
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s0 += __shfl_down(s0, o, 64);
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    sr[k] += __shfl_down(sr[k], o, 64);
-                    si[k] += __shfl_down(si[k], o, 64);
-                }
+            for (int k = 0; k < K; ++k) {
+                sr[k] = wave_sum(sr[k]);
+                si[k] = wave_sum(si[k]);
             }
             if (lane == 0) {
                 const size_t node = (size_t)Y * g.gx + X0 + Xw, plane = (size_t)g.gy * g.gx;
@@ -256,8 +254,7 @@ __global__ void __launch_bounds__(FR_W_THREADS) k_fr_level_partials(const float2
         const float v = h[e].x;
         if (v > best && v < INFINITY) best = v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_down(best, o, 64));
+    best = wave_max(best);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {

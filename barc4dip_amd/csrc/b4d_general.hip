@@ -254,8 +254,7 @@ __global__ void __launch_bounds__(256) k_half_peak(const float2* __restrict__ GT
         const double v = (double)g[(size_t)kx * ny].x;
         acc += (kx == 0 || 2 * kx == nx) ? v : 2.0 * v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) peak[blockIdx.x] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
@@ -328,21 +327,21 @@ int general_psd_autocorr(b4d_plan* pl, const float* frames, int batch, float* ps
         // both sides have in-register three-radix kernels (b4d_wiener_mr.hip): forward row pairs -> transposed half spectra,
         // one pass over the columns (forward, |F|^2, inverse; the column stays in LDS), inverse row pairs + PSD rows:
         // 3 passes and ~32 bytes per pixel where the route below makes 7 passes
-        // two-lane launch groups (Lanes, b4d_fft2d.hpp): lane l works in slot l (sub frames of ny nx complex words) of each buffer
+        // two-lane launch groups (Lanes, b4d_lanes.hpp): lane l works in slot l (sub frames of ny nx complex words) of each buffer
         Lanes ln;
-        int rc = ln.open(pl, st, batch, wmr_spectrum_elems(ny, nx) * sizeof(float2), (size_t)npix * sizeof(float),
+        int rc = ln.open(pl->lanes, pl->chunk, st, batch, wmr_spectrum_elems(ny, nx) * sizeof(float2), (size_t)npix * sizeof(float),
                          wmr_spectrum_elems(ny, nx) <= (size_t)npix, (size_t)8 << 20);   // a slot holds the transposed half spectra of its frames
         if (rc) return rc;
         int g = 0;
-        for (int b0 = 0; b0 < batch && rc == B4D_OK; b0 += ln.sub, ++g) {
+        for (int b0 = 0; b0 < batch; b0 += ln.sub, ++g) {
             const int nb = std::min(ln.sub, batch - b0);
             const size_t off = (size_t)b0 * npix, so = (size_t)ln.slot(g) * ln.sub * npix;
-            rc = wmr_psd_autocorr(frames + off, nb, ny, nx, pl->tw_x, pl->tw_y, pl->gbuf1 + so, reinterpret_cast<float*>(pl->gbuf2 + so),
-                                  reinterpret_cast<float*>(pl->gbuf3 + so), psd ? psd + off : nullptr, psd_scale,
-                                  autocorr ? autocorr + off : nullptr, flags, ln.stream(g));
+            if ((rc = wmr_psd_autocorr(frames + off, nb, ny, nx, pl->tw_x, pl->tw_y, pl->gbuf1 + so, reinterpret_cast<float*>(pl->gbuf2 + so),
+                                       reinterpret_cast<float*>(pl->gbuf3 + so), psd ? psd + off : nullptr, psd_scale,
+                                       autocorr ? autocorr + off : nullptr, flags, ln.stream(g))))
+                return rc;
         }
-        const int rj = ln.close();
-        return rc ? rc : rj;
+        return ln.close();
     }
     if (pl->large && pm_fusable(nx) && pm_fusable(ny)) {
         // half-spectrum path: pair rows -> transpose -> columns on nx/2 + 1 sequences -> |F|^2 (+ PSD) -> inverse columns ->
@@ -392,20 +391,21 @@ int general_psd_autocorr(b4d_plan* pl, const float* frames, int batch, float* ps
 int general_fft2d(b4d_plan* pl, const float* frames, int batch, float2* out, hipStream_t st) {
     const int ny = pl->ny, nx = pl->nx, npix = ny * nx;
     if (pl->wmr) {   // mixed-radix kernels on both sides (b4d_wiener_mr.hip)
-        // two-lane launch groups (Lanes, b4d_fft2d.hpp): lane l works in gbuf(1 + l)
+        // two-lane launch groups (Lanes, b4d_lanes.hpp): lane l works in gbuf(1 + l)
         const size_t selems = wmr_spectrum_elems(ny, nx);
         Lanes ln;
-        int rc = ln.open(pl, st, batch, selems * sizeof(float2), (size_t)npix * sizeof(float), true, (size_t)8 << 20);   // (lane 1 has a buffer of its own)
+        int rc = ln.open(pl->lanes, pl->chunk, st, batch, selems * sizeof(float2), (size_t)npix * sizeof(float), true,
+                         (size_t)8 << 20);   // (lane 1 has a buffer of its own)
         if (rc) return rc;
         int g = 0;
-        for (int b0 = 0; b0 < batch && rc == B4D_OK; b0 += ln.sub, ++g) {
+        for (int b0 = 0; b0 < batch; b0 += ln.sub, ++g) {
             const int nb = std::min(ln.sub, batch - b0);
             float2* T = ln.slot(g) ? pl->gbuf2 : pl->gbuf1;
-            rc = wmr_fft2d(frames + (size_t)b0 * npix, nb, ny, nx, pl->tw_x, pl->tw_y, T, reinterpret_cast<float*>(T + selems * nb),
-                           out + (size_t)b0 * npix, ln.stream(g));
+            if ((rc = wmr_fft2d(frames + (size_t)b0 * npix, nb, ny, nx, pl->tw_x, pl->tw_y, T, reinterpret_cast<float*>(T + selems * nb),
+                                out + (size_t)b0 * npix, ln.stream(g))))
+                return rc;
         }
-        const int rj = ln.close();
-        return rc ? rc : rj;
+        return ln.close();
     }
     for (int b0 = 0; b0 < batch; b0 += pl->chunk) {
         const int nb = std::min(pl->chunk, batch - b0);
@@ -445,29 +445,28 @@ int general_xcorr(b4d_plan* pl, const float* a, const float* b, int batch, float
     if (pl->wmr) {
         // mixed-radix kernels on both sides: two forward half-spectrum passes per operand, product + inverse columns, inverse
         // row pairs (b4d_wiener_mr.hip); the chunk buffers hold complex (chunk, ny, nx), twice a half spectrum
-        // two-lane launch groups (Lanes, b4d_fft2d.hpp; 2160 x 2560: 10.4 -> 11.5 k pairs/s): lane l works in slot l (sub frames of
+        // two-lane launch groups (Lanes, b4d_lanes.hpp; 2160 x 2560: 10.4 -> 11.5 k pairs/s): lane l works in slot l (sub frames of
         // ny nx complex words) of each buffer; a slot of gbuf3 holds G of its frames and the row-maxima scratch behind it
         const size_t selems = wmr_spectrum_elems(ny, nx);
         Lanes ln;
-        int rc = ln.open(pl, st, batch, selems * sizeof(float2), 2 * (size_t)npix * sizeof(float), selems + (size_t)ny <= (size_t)npix,
-                         (size_t)8 << 20);   // (groups of 2-4 frames at 2160 x 2560: measured best)
+        int rc = ln.open(pl->lanes, pl->chunk, st, batch, selems * sizeof(float2), 2 * (size_t)npix * sizeof(float),
+                         selems + (size_t)ny <= (size_t)npix, (size_t)8 << 20);   // (groups of 2-4 frames at 2160 x 2560: measured best)
         if (rc) return rc;
         int g = 0;
-        for (int b0 = 0; b0 < batch && rc == B4D_OK; b0 += ln.sub, ++g) {
+        for (int b0 = 0; b0 < batch; b0 += ln.sub, ++g) {
             const int nb = std::min(ln.sub, batch - b0);
             const size_t off = (size_t)b0 * npix, so = (size_t)ln.slot(g) * ln.sub * npix;
             hipStream_t ls = ln.stream(g);
             float2 *A = pl->gbuf1 + so, *B = pl->gbuf2 + so, *G = pl->gbuf3 + so;
             float* scratch = reinterpret_cast<float*>(G + selems * nb);
-            rc = wmr_forward_spectra(a + off, nb, ny, nx, pl->tw_x, pl->tw_y, A, scratch, ls);
-            if (rc == B4D_OK) rc = wmr_forward_spectra(b + off, nb, ny, nx, pl->tw_x, pl->tw_y, B, scratch, ls);
-            if (rc == B4D_OK) rc = wmr_product_inverse(A, B, nullptr, nullptr, nb, ny, nx, pl->tw_y, G, 0, 0.f, flags & B4D_REMOVE_MEAN, ls);
-            if (rc == B4D_OK) rc = wmr_rows_real_out(G, nb, ny, nx, pl->tw_x, corr + off, ls);
-            if (rc == B4D_OK && (flags & B4D_NORM_PEAK))
-                rc = normalise_by_absmax(corr + off, (size_t)npix, nb, reinterpret_cast<float*>(A), ls);
+            if ((rc = wmr_forward_spectra(a + off, nb, ny, nx, pl->tw_x, pl->tw_y, A, scratch, ls))) return rc;
+            if ((rc = wmr_forward_spectra(b + off, nb, ny, nx, pl->tw_x, pl->tw_y, B, scratch, ls))) return rc;
+            if ((rc = wmr_product_inverse(A, B, nullptr, nullptr, nb, ny, nx, pl->tw_y, G, 0, 0.f, flags & B4D_REMOVE_MEAN, ls))) return rc;
+            if ((rc = wmr_rows_real_out(G, nb, ny, nx, pl->tw_x, corr + off, ls))) return rc;
+            if (flags & B4D_NORM_PEAK)
+                if ((rc = normalise_by_absmax(corr + off, (size_t)npix, nb, reinterpret_cast<float*>(A), ls))) return rc;
         }
-        const int rj = ln.close();
-        return rc ? rc : rj;
+        return ln.close();
     }
     for (int b0 = 0; b0 < batch; b0 += pl->chunk) {
         const int nb = std::min(pl->chunk, batch - b0);

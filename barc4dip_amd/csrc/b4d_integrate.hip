@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -138,25 +139,6 @@ struct WfFit {
 };
 constexpr int WF_FIT_THREADS = 1024;
 
-template <int NV, int NT = WF_FIT_THREADS>
-__device__ __forceinline__ void wf_block_sum(double (&v)[NV], double (*sh)[NV]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-        if (lane == 0) sh[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) {
-            double s = 0.0;
-            for (int w = 0; w < NT / 64; ++w) s += sh[w][k];
-            v[k] = s;
-        }
-}
-
 __global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_moments(const float* __restrict__ w, int ny, int nx, WfFit f,
                                                                      double* __restrict__ coeff) {
     __shared__ double sh[WF_FIT_THREADS / 64][6];
@@ -173,7 +155,7 @@ __global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_moments(const float
         s[4] += u * v * x;
         s[5] += v * v * x;
     }
-    wf_block_sum<6>(s, sh);
+    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
     if (threadIdx.x == 0)
         for (int a = 0; a < 6; ++a) {
             double c = 0.0;
@@ -204,7 +186,7 @@ __global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_residual(const floa
         s[0] += (double)out;
         s[1] += (double)out * (double)out;
     }
-    wf_block_sum<2>(s, sh);
+    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
     if (threadIdx.x == 0) {
         const double mean = s[0] / npix;
         rms[blockIdx.x] = sqrt(fmax(0.0, s[1] / npix - mean * mean));
@@ -492,7 +474,7 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wsetup(const float* __res
         x[fo + e] = 0.f;
         s[0] += (double)b * (double)b;
     }
-    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    block_sum(s, &sh[0][0], WF_PCG_THREADS / 64);
     if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
 }
 
@@ -518,7 +500,7 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wapply(WfPcg g, int slot)
         g.qz[fo + e] = a;
         s[0] += (double)pc * (double)a;
     }
-    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    block_sum(s, &sh[0][0], WF_PCG_THREADS / 64);
     if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
 }
 
@@ -543,7 +525,7 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wupdate(WfPcg g, int slot
         g.r[fo + e] = r;
         s[0] += (double)r * (double)r;
     }
-    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    block_sum(s, &sh[0][0], WF_PCG_THREADS / 64);
     if (threadIdx.x == 0) g.part_b[(size_t)map * g.nb + blockIdx.x] = s[0];
 }
 
@@ -557,7 +539,7 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wdot(WfPcg g, int slot, i
     double s[1] = {0.0};
     for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS)
         s[0] += (double)g.r[fo + e] * (double)g.qz[fo + e];
-    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    block_sum(s, &sh[0][0], WF_PCG_THREADS / 64);
     if (threadIdx.x == 0) g.part_c[(size_t)map * g.nb + blockIdx.x] = s[0];
 }
 
@@ -635,29 +617,6 @@ __device__ __forceinline__ float wf_fit_weight(const float* __restrict__ w, int 
     return (a > 0.f && isfinite(a)) ? a : 0.f;
 }
 
-// wf_block_sum for many sums: lane k adds column k of the wave results (same order, wave 0 first), so that thread 0 does not hold
-// NV x waves loads in registers at once
-template <int NV, int NT>
-__device__ __forceinline__ void wf_block_sum_columns(double (&v)[NV], double (*sh)[NV]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-        if (lane == 0) sh[wave][k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < NV) {
-        double s = 0.0;
-        for (int w = 0; w < NT / 64; ++w) s += sh[w][threadIdx.x];
-        sh[0][threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) v[k] = sh[0][k];
-}
-
 __global__ void __launch_bounds__(WF_WFIT_THREADS) k_wf_poly2_wmoments(const float* __restrict__ phi, const float* __restrict__ w,
                                                                       long long w_stride, int ny, int nx, WfFit f,
                                                                       double* __restrict__ coeff) {
@@ -692,7 +651,14 @@ __global__ void __launch_bounds__(WF_WFIT_THREADS) k_wf_poly2_wmoments(const flo
         s[19] += u * v * x;
         s[20] += v * v * x;
     }
-    wf_block_sum_columns<21, WF_WFIT_THREADS>(s, sh);
+    {   // lane k adds column k of the wave sums (thread 0 would hold 21 x 16 loads at once), thread 0 collects them
+        const double t = block_sum_columns(s, &sh[0][0], WF_WFIT_THREADS / 64);
+        if (threadIdx.x < 21) sh[0][threadIdx.x] = t;
+        __syncthreads();
+        if (threadIdx.x == 0)
+#pragma unroll
+            for (int k = 0; k < 21; ++k) s[k] = sh[0][k];
+    }
     if (threadIdx.x == 0) {
         constexpr int pu[6] = {0, 1, 0, 2, 1, 0}, pv[6] = {0, 0, 1, 0, 1, 2};
 #pragma unroll
@@ -739,7 +705,7 @@ __global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_wresidual(const flo
             s[2] += (double)wf * (double)out * (double)out;
         }
     }
-    wf_block_sum<3>(s, sh);
+    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
     if (threadIdx.x == 0) {
         const double mean = s[0] > 0.0 ? s[1] / s[0] : 0.0;
         rms[blockIdx.x] = s[0] > 0.0 ? sqrt(fmax(0.0, s[2] / s[0] - mean * mean)) : __builtin_nan("");
@@ -870,7 +836,7 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_unwrap_wsetup(const float
         x[fo + e] = 0.f;
         s[0] += (double)b * (double)b;
     }
-    wf_block_sum<1, WF_PCG_THREADS>(s, sh);
+    block_sum(s, &sh[0][0], WF_PCG_THREADS / 64);
     if (threadIdx.x == 0) g.part_a[(size_t)map * g.nb + blockIdx.x] = s[0];
 }
 

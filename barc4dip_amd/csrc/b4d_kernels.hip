@@ -66,48 +66,6 @@ std::atomic<int> g_opt_colsets{1};   // "colsets": column-set tiles between the 
 int spectrum_rows_last(const b4d_plan* pl, float2* spec, const float* frames, int batch, float2* out, hipStream_t st);
 }  // namespace b4d
 
-int Lanes::open(b4d_plan* p, hipStream_t s, int batch, size_t inter_bytes, size_t frame_bytes, bool allow_two, size_t min_group_bytes) {
-    pl = p;
-    st = s;
-    const int want = (int)std::max<size_t>(1, ((size_t)64 << 20) / std::max<size_t>(1, inter_bytes));
-    // two lanes need two slots of the workspaces and enough work to pay for the fork / join (a few microseconds of host time)
-    two = allow_two && b4d::g_opt_lanes.load() != 0 && batch >= 2 && p->chunk >= 2 && (size_t)batch * frame_bytes >= 2 * min_group_bytes &&
-          (size_t)std::min(want, p->chunk / 2) * frame_bytes >= min_group_bytes;
-    sub = two ? std::min(want, p->chunk / 2) : p->chunk;   // one lane: the plan's own groups
-    if (two) {   // an even number of groups of equal size
-        int groups = (batch + sub - 1) / sub;
-        groups += groups & 1;
-        sub = (batch + groups - 1) / groups;
-    }
-    return fork(p, s, two);
-}
-
-int Lanes::fork(b4d_plan* p, hipStream_t s, bool want_two) {
-    pl = p;
-    st = s;
-    two = want_two && b4d::g_opt_lanes.load() != 0;
-    if (!two) return B4D_OK;
-    if (!p->aux) {
-        const int rs = b4d::lane_stream(0, &p->aux);
-        if (rs) return rs;
-    }
-    if (!p->ev_fork) B4D_HIP(hipEventCreateWithFlags(&p->ev_fork, hipEventDisableTiming));
-    if (!p->ev_join) B4D_HIP(hipEventCreateWithFlags(&p->ev_join, hipEventDisableTiming));
-    B4D_HIP(hipEventRecord(p->ev_fork, st));
-    B4D_HIP(hipStreamWaitEvent(p->aux, p->ev_fork, 0));
-    return B4D_OK;
-}
-
-int Lanes::close() {
-    if (!two) return B4D_OK;
-    B4D_HIP(hipEventRecord(pl->ev_join, pl->aux));
-    B4D_HIP(hipStreamWaitEvent(st, pl->ev_join, 0));
-    return B4D_OK;
-}
-
-namespace b4d {
-}  // namespace b4d
-
 extern "C" {
 
 const char* b4d_version(void) { return "b4d 0.3.0 (gfx950)" B4D_VERSION_SUFFIX; }
@@ -226,9 +184,9 @@ int b4d_plan_destroy(b4d_plan* p) {
     if (p->nyq_rows) (void)hipFree(p->nyq_rows);
     if (p->gnyq) (void)hipFree(p->gnyq);
     if (p->track_ws) (void)hipFree(p->track_ws);
-    if (p->aux) (void)hipStreamSynchronize(p->aux);   // the library's shared lane stream: not destroyed with the plan
-    if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
-    if (p->ev_join) (void)hipEventDestroy(p->ev_join);
+    if (p->lanes.aux) (void)hipStreamSynchronize(p->lanes.aux);   // the library's shared lane stream: not destroyed with the plan
+    if (p->lanes.ev_fork) (void)hipEventDestroy(p->lanes.ev_fork);
+    if (p->lanes.ev_join) (void)hipEventDestroy(p->lanes.ev_join);
     for (float2* q : {p->wx, p->wy, p->gbuf1, p->gbuf2, p->gbuf3})
         if (q) (void)hipFree(q);
     delete p;
@@ -276,12 +234,12 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
         B4D_HIP(hipEventRecord(e, st));
         return B4D_OK;
     };
-    // 4096^2 frames (and larger pixel counts): the launch groups are dealt to two lanes (Lanes, b4d_fft2d.hpp), half the plan's chunk
+    // 4096^2 frames (and larger pixel counts): the launch groups are dealt to two lanes (Lanes, b4d_lanes.hpp), half the plan's chunk
     // each, every lane in its own slot of the workspaces: 9.2 -> 9.75 k frames/s (tools/dev_pipe_chunk.py).  Not at 2048^2 and
     // below (+1 % ... 0: the column kernel owns the CUs' register files and nothing runs under it), and never on the timed variant.
     int rc = B4D_OK;
     Lanes ln;
-    if ((rc = ln.fork(pl, st, !kernel_ms && fpix >= (size_t)4096 * 4096 && pl->chunk >= 2 && batch >= 2))) return rc;
+    if ((rc = ln.fork(pl->lanes, st, !kernel_ms && fpix >= (size_t)4096 * 4096 && pl->chunk >= 2 && batch >= 2))) return rc;
     ln.sub = ln.two ? std::max(1, std::min(pl->chunk / 2, (batch + 1) / 2)) : pl->chunk;
     const size_t half = fpix / 2;
     int grp = 0;
@@ -332,10 +290,7 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
         }
         if ((rc = mark())) break;
     }
-    {
-        const int rj = ln.close();
-        if (rc == B4D_OK) rc = rj;
-    }
+    if (rc == B4D_OK) rc = ln.close();   // (after a failure the destructor joins)
     if (kernel_ms && rc == B4D_OK && !ev.empty()) {
         hipError_t e = hipEventSynchronize(ev.back());
         if (e != hipSuccess) rc = fail(B4D_EHIP, std::string("hipEventSynchronize: ") + hipGetErrorString(e));
@@ -453,15 +408,16 @@ int b4d_fft2d(b4d_plan* pl, const float* frames, int batch, float* out_c64, void
     // frame is a group of its own and stays on one lane (12.0 -> 13.8 k frames/s; 13.1 k on two).
     const size_t fpix = (size_t)pl->ny * pl->nx, half = fpix / 2;
     Lanes ln;
-    int rc = ln.open(pl, st, batch, half * sizeof(float2), fpix * sizeof(float), fpix < (size_t)4096 * 4096, (size_t)32 << 20);
-    if (!ln.two && fpix == (size_t)4096 * 4096) ln.sub = 1;
+    int rc = ln.open(pl->lanes, pl->chunk, st, batch, half * sizeof(float2), fpix * sizeof(float), fpix < (size_t)4096 * 4096,
+                     (size_t)32 << 20);
     if (rc) return rc;
+    if (!ln.two && fpix == (size_t)4096 * 4096) ln.sub = 1;
     int g = 0;
-    for (int b0 = 0; b0 < batch && rc == B4D_OK; b0 += ln.sub, ++g)
-        rc = spectrum_rows_last(pl, pl->spec + (size_t)ln.slot(g) * ln.sub * half, frames + b0 * fpix, std::min(ln.sub, batch - b0),
-                                reinterpret_cast<float2*>(out_c64) + b0 * fpix, ln.stream(g));
-    const int rj = ln.close();
-    return rc ? rc : rj;
+    for (int b0 = 0; b0 < batch; b0 += ln.sub, ++g)
+        if ((rc = spectrum_rows_last(pl, pl->spec + (size_t)ln.slot(g) * ln.sub * half, frames + b0 * fpix, std::min(ln.sub, batch - b0),
+                                     reinterpret_cast<float2*>(out_c64) + b0 * fpix, ln.stream(g))))
+            return rc;
+    return ln.close();
 }
 
 int b4d_fft2d_c2c(b4d_plan* pl, const float* in_c64, int batch, int inverse, float* out_c64, void* stream) {

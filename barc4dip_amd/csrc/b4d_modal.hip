@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -413,19 +414,8 @@ __global__ void __launch_bounds__(MD_THREADS) k_modal_apply(const float* maps, c
         }
     }
     if (!sums) return;
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s[k] += __shfl_down(s[k], o, 64);
-        if (lane == 0) sh[wave][k] = s[k];
-    }
-    __syncthreads();
-    if (tid < 3) {
-        double t = 0.0;
-        for (int wv = 0; wv < MD_THREADS / 64; ++wv) t += sh[wv][tid];
-        sums[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + tid] = t;
-    }
+    const double t = block_sum_columns(s, &sh[0][0], MD_THREADS / 64);
+    if (tid < 3) sums[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3 + tid] = t;
 }
 
 // rms = sqrt(sum w r^2 / sum w - (sum w r / sum w)^2), NaN without a valid node; one thread per map adds the blocks in order

@@ -28,6 +28,7 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -96,13 +97,6 @@ static int mt_levels(long long T, int m, int max_level) {
     int L = 1;
     while (L < 40 && (T >> L) >= m / 2 + 1 && (max_level < 0 || L <= max_level)) ++L;
     return L;
-}
-
-// the same bits in every lane: lane l and its partner add the same two numbers at every step
-__device__ __forceinline__ double mt_xsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // ---- scan: grid (ceil(npix / 256), ceil(n / 32)).  Every writer stores the same byte.
@@ -250,7 +244,7 @@ __global__ void __launch_bounds__(64) k_mt_push(const float* __restrict__ src, l
             const int a = c + k + u;        // the frame's index in its level; the branches below are the same in every lane
             if (k + u < n) {
                 if (a < M - 1) {
-                    const double s = mt_xsum((double)v);
+                    const double s = wave_sum_all((double)v);
                     if (lane == 0) head[(size_t)a * W + w] = s;
                 }
                 if (out && (a & 1)) {
@@ -272,13 +266,13 @@ __global__ void __launch_bounds__(64) k_mt_push(const float* __restrict__ src, l
     }
 #pragma unroll
     for (int j = 0; j < NL; ++j) {
-        const double a = mt_xsum(pd[j]), b = mt_xsum(qd[j]);
+        const double a = wave_sum_all(pd[j]), b = wave_sum_all(qd[j]);
         if (lane == 0) {
             P[(size_t)j * W + w] += a;
             Qs[(size_t)j * W + w] += b;
         }
     }
-    sd = mt_xsum(sd);
+    sd = wave_sum_all(sd);
     if (lane == 0) S[w] += sd;
 }
 
@@ -292,7 +286,7 @@ __global__ void __launch_bounds__(64) k_mt_tail(const float* __restrict__ ring, 
     const float* rl = ring + (size_t)l * m * (size_t)Q + (size_t)(64ll * w + lane);
     for (int i = 0; i < m - 1; ++i) {
         const int idx = Tl - 1 - i;
-        const double s = mt_xsum(idx >= 0 ? (double)rl[(size_t)(idx & (m - 1)) * (size_t)Q] : 0.0);
+        const double s = wave_sum_all(idx >= 0 ? (double)rl[(size_t)(idx & (m - 1)) * (size_t)Q] : 0.0);
         if (lane == 0) tail[((size_t)l * m + i) * W + w] = s;
     }
 }

@@ -3,35 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "b4d_reduce.hpp"   // argmax_merge, block_argmax
+
 namespace b4d {
-
-// (value, flat index) arg-max with NumPy's first-occurrence rule: larger value wins, ties go to the lower index
-__device__ __forceinline__ void argmax_merge(float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-        v = ov;
-        i = oi;
-    }
-}
-
-// Block-wide arg-max by the same rule: every lane brings its own (bv, bi) and every lane returns with the merged pair of the
-// workgroup.  sv / si: LDS, one word per wave (nwaves = blockDim.x / 64).  It contains a barrier: the WHOLE workgroup must
-// call it, and sv / si must not be written again before the workgroup's next barrier.
-__device__ __forceinline__ void block_argmax(float& bv, int& bi, float* sv, int* si, int nwaves) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_down(bv, o, 64);
-        const int oi = __shfl_down(bi, o, 64);
-        argmax_merge(bv, bi, ov, oi);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sv[threadIdx.x >> 6] = bv;
-        si[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
-    bv = sv[0];
-    bi = si[0];
-    for (int k = 1; k < nwaves; ++k) argmax_merge(bv, bi, sv[k], si[k]);
-}
 
 // One lane: peak, snr = |peak| / (median + eps) and the sub-pixel shift of the arg-max (mi, mj) of an mny x mnx map,
 // op for op like tracking.py:314-375 (float32 scalars, no contraction).  c(di, dj) returns the map value at

@@ -501,15 +501,12 @@ static int pm_fused_launch2(const PmAxis& ax, const void* x, float2* out, int S,
                             const FusedIO& io, hipStream_t st) {
     const bool onebuf = pm_onebuf(P, ax.A, ax.B);
     const size_t lds = sizeof(float2) * pm_lds_elems(P, ax.A, ax.B, onebuf);
-    if (int rc_lds = ensure_dynamic_lds(reinterpret_cast<const void*>(onebuf ? &k_pm_fused<P, IN, OUT, true> : &k_pm_fused<P, IN, OUT, false>),
-                                        150 * 1024))
-        return rc_lds;
-    if (onebuf)
-        hipLaunchKernelGGL((k_pm_fused<P, IN, OUT, true>), dim3(S), dim3(FT_ONEBUF), lds, st, x, out, ax.tw, ax.A, ax.B, filt, conj_io, scale, io);
-    else
-        hipLaunchKernelGGL((k_pm_fused<P, IN, OUT, false>), dim3(S), dim3(FT_MAX), lds, st, x, out, ax.tw, ax.A, ax.B, filt, conj_io, scale, io);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    // the attribute is asked for once at a fixed 150 KiB, whatever this call needs (launch() then finds it set)
+    auto go = [&](auto kernel, int threads) -> int {
+        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), 150 * 1024)) return rc;
+        return launch(kernel, dim3(S), dim3(threads), lds, st, x, out, ax.tw, ax.A, ax.B, filt, conj_io, scale, io);
+    };
+    return onebuf ? go(&k_pm_fused<P, IN, OUT, true>, FT_ONEBUF) : go(&k_pm_fused<P, IN, OUT, false>, FT_MAX);
 }
 
 // the compiled load / store pairs of k_pm_fused

@@ -15,6 +15,7 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 #include "b4d_rankfilt.hpp"
 
 namespace b4d {
@@ -120,11 +121,9 @@ __device__ __forceinline__ void medians4(uint32_t (&w)[S][12], uint32_t (&med)[4
 // is already as wide: the pair only ever widens, so a stale read costs an atomic and never loses one (a frame's workgroups would
 // otherwise queue a thousand atomics on one line).
 __device__ __forceinline__ void reduce_range(uint32_t kmin, uint32_t kmax, uint32_t* s_mm, uint32_t* __restrict__ mm_frame) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, d));
-        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, d));
-    }
+    kmin = wave_min_all(kmin);
+    kmax = wave_max_all(kmax);
+    // (no block reduction of b4d_reduce.hpp behind it: the waves meet in integer atomics, whose order does not matter)
     if ((threadIdx.x & 63) == 0 && kmin <= kmax) {
         atomicMin(&s_mm[0], kmin);
         atomicMax(&s_mm[1], kmax);
@@ -323,8 +322,7 @@ __global__ void __launch_bounds__(256) k_despeckle(const float* __restrict__ in,
         }
     }
     if (counts) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) cnt += (unsigned)__shfl_xor((int)cnt, d);
+        cnt = wave_sum_all(cnt);
         if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
         __syncthreads();
         if (threadIdx.x == 0 && s_cnt) atomicAdd(counts + blockIdx.z, (unsigned long long)s_cnt);

@@ -70,6 +70,7 @@ __device__ inline unsigned radix_select(const float* __restrict__ x, unsigned n,
             const int per = 2048 / 64;
             unsigned s = 0;
             for (int i = 0; i < per; ++i) s += hist[threadIdx.x * per + i];
+            // (wave_scan_inclusive of b4d_reduce.hpp, kept inline: through the helper the tracking epilogues' instructions come out different)
             unsigned incl = s;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
@@ -146,6 +147,7 @@ __device__ inline unsigned next_larger_key(const float* __restrict__ x, unsigned
         visit(a.x); visit(a.y); visit(a.z); visit(a.w);
     }
     for (unsigned j = 4 * n4 + threadIdx.x; j < n; j += blockDim.x) visit(x[j]);
+    // (wave_min of b4d_reduce.hpp, kept inline for the same reason)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const unsigned t = __shfl_down(best, o, 64);

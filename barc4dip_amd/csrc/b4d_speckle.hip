@@ -15,6 +15,7 @@
 #include <string>
 
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -41,23 +42,6 @@ struct SpeckleArgs {
     int order, taper;
     double* out;             // (npairs, gy, gx, 6)
 };
-
-// sum of SC_NSUM doubles over the workgroup (<= 4 waves) in a fixed order, result in every lane
-__device__ inline void sc_block_sum(double (&v)[SC_NSUM], double* red) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
-#pragma unroll
-    for (int k = 0; k < SC_NSUM; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o, 64);
-        if (lane == 0) red[wave * SC_NSUM + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < SC_NSUM; ++k) {
-        v[k] = 0.0;
-        for (int i = 0; i < nwave; ++i) v[k] += red[i * SC_NSUM + k];
-    }
-}
 
 // integer tap t and the weights of the taps t and t + 1 along one axis; w0 is never 0 (a fraction that rounds to 1 moves the tap)
 __device__ inline void sc_taps(double d, int order, double& t, double& w0, double& w1) {
@@ -135,7 +119,7 @@ __global__ void __launch_bounds__(SC_THREADS) k_speckle_contrast(SpeckleArgs a) 
             ++j;
         }
     }
-    sc_block_sum(s, red);
+    block_sum_all(s, red, blockDim.x >> 6);   // (<= 4 waves) fixed order, result in every lane
     if (tid != 0) return;
 
     const double mr = s[1] / s[0], ms = s[3] / s[0];

@@ -15,6 +15,7 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 #include "b4d_select.hpp"
 
 namespace b4d {
@@ -48,34 +49,6 @@ int get_scratch(size_t bytes, void** out, hipStream_t stream) {
     }
     *out = sc.p;
     return B4D_OK;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-// block-wide sum of K doubles per lane; result valid in thread 0.  blockDim.x <= 1024.
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double* sh /* [16*K] */) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        v[k] = wave_sum(v[k]);
-        if (lane == 0) sh[w * K + k] = v[k];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            double s = 0.0;
-            for (int i = 0; i < nw; ++i) s += sh[i * K + k];
-            v[k] = s;
-        }
-    }
-    __syncthreads();
 }
 
 // ------------------------------------------------------------------------------------ temporal
@@ -239,7 +212,8 @@ __global__ void __launch_bounds__(1024) k_moments1(const float* __restrict__ fra
             v[3] += (x >= sat) ? 1.0 : 0.0;
         }
     }
-    block_sum<4>(v, sh);
+    block_sum(v, sh, (blockDim.x + 63) >> 6);
+    __syncthreads();
     if (threadIdx.x == 0) {
         double* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 4;
 #pragma unroll
@@ -288,7 +262,8 @@ __global__ void __launch_bounds__(1024) k_moments2(const float* __restrict__ fra
             v[2] = fma(d2, d2, v[2]);
         }
     }
-    block_sum<3>(v, sh);
+    block_sum(v, sh, (blockDim.x + 63) >> 6);
+    __syncthreads();
     if (threadIdx.x == 0) {
         double* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
         o[0] = v[0];
@@ -377,7 +352,8 @@ __global__ void __launch_bounds__(256) k_sobel_fin(const double* __restrict__ pa
     for (int i = threadIdx.x; i < nblk; i += blockDim.x)
 #pragma unroll
         for (int k = 0; k < 5; ++k) v[k] += p[(size_t)i * 5 + k];
-    block_sum<5>(v, sh);
+    block_sum(v, sh, (blockDim.x + 63) >> 6);
+    __syncthreads();
     if (threadIdx.x == 0) {
         double* o = out + (size_t)blockIdx.x * 4;
         const double n = v[0];
@@ -425,8 +401,7 @@ __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ 
     const unsigned n_all = (unsigned)npix;
     unsigned c = 0;
     for (unsigned i = threadIdx.x; i < n_all; i += blockDim.x) c += (x[i] == x[i]) ? 1u : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = c;
     __syncthreads();
     unsigned n = 0;
@@ -516,12 +491,7 @@ __global__ void __launch_bounds__(64) k_pctm_pick(PctMulti p) {
     const int per = 2048 / 64;
     unsigned s = 0;
     for (int i = 0; i < per; ++i) s += g[lane * per + i];
-    unsigned incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += t;
-    }
+    const unsigned incl = wave_scan_inclusive(s, lane);
     const unsigned total = __shfl(incl, 63, 64);
     unsigned kk;
     if (PASS == 0) {
@@ -583,11 +553,7 @@ __global__ void __launch_bounds__(256) k_pctm_next(PctMulti p) {
         const unsigned key = f2key(v);
         if (key > ka && key < best) best = key;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned t = __shfl_down(best, o, 64);
-        best = t < best ? t : best;
-    }
+    best = wave_min(best);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -712,7 +678,8 @@ __global__ void __launch_bounds__(256) k_psd_stats1(PsdStatArgs a, double fmax) 
             }
         }
     }
-    block_sum<7>(v, sh);
+    block_sum(v, sh, (blockDim.x + 63) >> 6);
+    __syncthreads();
     if (threadIdx.x == 0) {
         double* o = a.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8;
 #pragma unroll
@@ -980,10 +947,12 @@ int b4d_psd_stats(const float* psd, int batch, int ny, int nx, double* out, void
     // f_max = min(max|fx|, max|fy|) of the shifted fftfreq axes
     auto amax = [](int n) { return (double)(n / 2) / (double)n; };
     const double fmax = std::fmin(amax(nx), amax(ny));
-    hipLaunchKernelGGL(k_psd_stats1, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.ncoarse, st, a, fmax);
+    // dynamic LDS of the ring histograms, square maps only; nx has no upper limit at this entry point: k_psd_stats1 takes
+    // 8 (nx / 2 + 2) bytes (64 KiB passed from nx = 16 382), k_psd_stats2 8 (nx + 5) bytes (passed from nx = 8 188)
+    if ((rc = launch(k_psd_stats1, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.ncoarse, st, a, fmax))) return rc;
     hipLaunchKernelGGL(k_psd_stats_mid, dim3(batch), dim3(64), 0, st, a, out, ring, below);
     if (square) {
-        hipLaunchKernelGGL(k_psd_stats2, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.nfine, st, a, fmax);
+        if ((rc = launch(k_psd_stats2, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.nfine, st, a, fmax))) return rc;
         hipLaunchKernelGGL(k_psd_stats_fin, dim3(batch), dim3(64), 0, st, a, ring, below, out);
     }
     B4D_HIP(hipGetLastError());

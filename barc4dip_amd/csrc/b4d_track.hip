@@ -9,12 +9,12 @@
 //   epilogue     first-occurrence arg-max, exact median by radix select, 3x3 Taylor step: k_track_fin (three passes on the
 //                map) or, where the map kernel has counted and gathered the expected median bin, k_track_select (verdict per
 //                pair) + k_track_fin2 (passes 2-3 on the bin) with k_track_fin behind it for the pairs left over.  The two
-//                share fin_map, fin_argmax (block_argmax, b4d_peak.hpp), median_from_select and track_finish.
+//                share fin_map, fin_argmax (block_argmax, b4d_reduce.hpp), median_from_select and track_finish.
 // Image spectra are computed once and reused by every template (the reference re-transforms
 // the same frame 18 times per time step, metrics/speckles.py:347-415).
 // Three phase-correlation routes (power-of-two, mixed-radix, DFT-matrix) and template matching share the host side: the
 // workspace of an entry point is ONE layout run twice (track_workspace), the sources are validated, uploaded and z-scored by
-// track_sources, and every kernel goes through launch().
+// track_sources, and every kernel goes through launch() (b4d_common.hpp).
 #include <cstring>
 
 #include "b4d_fft2d.hpp"
@@ -23,17 +23,6 @@
 #include "b4d_wiener_mr.hpp"
 
 namespace b4d {
-
-// Every launch of this unit: the dynamic-LDS attribute where the kernel uses dynamic LDS (ensure_dynamic_lds, b4d_common.hpp),
-// the launch, and its one error check.  The arguments are converted to the kernel's own parameter types.
-template <class... P, class... A>
-static int launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const A&... args) {
-    if (lds)
-        if (const int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return rc;
-    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
 
 // ------------------------------------------------------------------------------------ ROI statistics
 // Population mean / std of every ROI in float64, stored as float like NumPy's float32 arithmetic does:
@@ -74,6 +63,7 @@ __global__ void __launch_bounds__(256) k_roi_part(const float* __restrict__ fram
             a2 = fma(d, d, a2);
         }
     }
+    // (two wave_sum of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         a1 += __shfl_down(a1, o, 64);
@@ -558,11 +548,8 @@ __global__ void __launch_bounds__(1024) k_tpl_stats(const float* __restrict__ fr
         a1 += v;
         a2 = fma(v, v, a2);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a1 += __shfl_down(a1, o, 64);
-        a2 += __shfl_down(a2, o, 64);
-    }
+    a1 = wave_sum(a1);
+    a2 = wave_sum(a2);
     if ((threadIdx.x & 63) == 0) {
         sh[threadIdx.x >> 6] = a1;
         sh[16 + (threadIdx.x >> 6)] = a2;
@@ -671,12 +658,7 @@ __global__ void __launch_bounds__(256) k_ncc_sample(NccArgs p, unsigned* __restr
         const unsigned total = sh_total, k = total / 2;
         unsigned sum = 0;
         for (int b = 0; b < 16; ++b) sum += hist[16 * threadIdx.x + b];
-        unsigned incl = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned t = __shfl_up(incl, o, 64);
-            if ((int)threadIdx.x >= o) incl += t;
-        }
+        const unsigned incl = wave_scan_inclusive(sum, (int)threadIdx.x);
         if (total == 0u && threadIdx.x == 0) pred[pair] = 0u;
         unsigned below = incl - sum;
         if (total != 0u && k >= below && k < incl)
@@ -835,8 +817,7 @@ __global__ void __launch_bounds__(1024) k_absmax_part(const float* __restrict__ 
     float m = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         m = fmaxf(m, fabsf(f[i]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1199,29 +1180,28 @@ int b4d_xcorr2d(b4d_plan* pl, const float* a, const float* b, int batch, float* 
         part0 = ar.take<float>((size_t)256 * chunk);
     });
     if (rc) return rc;
-    // two-lane launch groups (Lanes, b4d_fft2d.hpp): 2048^2 16.3 -> 17.1 k pairs/s, 1024^2 50.5 -> 54.7 k (tools/dev_xcorr_chunk.py);
+    // two-lane launch groups (Lanes, b4d_lanes.hpp): 2048^2 16.3 -> 17.1 k pairs/s, 1024^2 50.5 -> 54.7 k (tools/dev_xcorr_chunk.py);
     // lane l works in slot l (sub items) of every chunk buffer
     // (groups of half the plan's chunk: the column kernels of this route want thousands of tiles per launch, 4-frame groups lose)
     Lanes ln;
     const bool two = chunk >= 2 && batch >= 2 && (size_t)batch * fpix * sizeof(float) >= ((size_t)32 << 20);
-    if ((rc = ln.fork(pl, st, two))) return rc;
+    if ((rc = ln.fork(pl->lanes, st, two))) return rc;
     ln.sub = ln.two ? std::max(1, std::min(chunk / 2, (batch + 1) / 2)) : chunk;
     int grp = 0;
-    for (int b0 = 0; b0 < batch && rc == B4D_OK; b0 += ln.sub, ++grp) {
+    for (int b0 = 0; b0 < batch; b0 += ln.sub, ++grp) {
         const int nb = std::min(ln.sub, batch - b0);
         const size_t so = (size_t)ln.slot(grp) * ln.sub;
         hipStream_t ls = ln.stream(grp);
         float2 *sa_ = sa + half * so, *sb_ = sb + half * so, *g_ = g + half * so, *fa_ = fa + ny * so, *fb_ = fb + ny * so;
         float *ra_ = ra_rows + ny * so, *rb_ = rb_rows + ny * so, *gn_ = gnyq + ny * so, *part = part0 + 256 * so;
-        if ((rc = forward_spectra(pl, a + b0 * fpix, nullptr, nb, sa_, ra_, fa_, ls))) break;
-        if ((rc = forward_spectra(pl, b + b0 * fpix, nullptr, nb, sb_, rb_, fb_, ls))) break;
-        if ((rc = product_inverse<false>(pl, sa_, fa_, nullptr, nullptr, sb_, fb_, nb, g_, gn_, 0.f, flags, ls))) break;
-        if ((rc = dispatch_c2r(pl, row_out_args(pl, g_, gn_, corr + b0 * fpix), nb, ls, C2R_OUT))) break;
+        if ((rc = forward_spectra(pl, a + b0 * fpix, nullptr, nb, sa_, ra_, fa_, ls))) return rc;
+        if ((rc = forward_spectra(pl, b + b0 * fpix, nullptr, nb, sb_, rb_, fb_, ls))) return rc;
+        if ((rc = product_inverse<false>(pl, sa_, fa_, nullptr, nullptr, sb_, fb_, nb, g_, gn_, 0.f, flags, ls))) return rc;
+        if ((rc = dispatch_c2r(pl, row_out_args(pl, g_, gn_, corr + b0 * fpix), nb, ls, C2R_OUT))) return rc;
         if (flags & B4D_NORM_PEAK)
-            if ((rc = normalise_by_absmax(corr + b0 * fpix, fpix, nb, part, ls))) break;
+            if ((rc = normalise_by_absmax(corr + b0 * fpix, fpix, nb, part, ls))) return rc;
     }
-    const int rj = ln.close();
-    return rc ? rc : rj;
+    return ln.close();
 }
 
 int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const float* tpl_src, int ntplsrc,
@@ -1238,7 +1218,7 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
     const int ny = pl->ny, nx = pl->nx;
     const int predict_mode = g_opt_track_predict.load();   // one route per call
     const size_t fpix = (size_t)ny * nx, half = fpix / 2;
-    // pairs per launch group; a call of more than one group runs on two lanes (Lanes, b4d_fft2d.hpp: alternate groups on the
+    // pairs per launch group; a call of more than one group runs on two lanes (Lanes, b4d_lanes.hpp: alternate groups on the
     // caller's stream and the library's second one, each with its own slot of the per-group buffers)
     const int pc_one = std::max(1, std::min(npairs, pl->chunk * 4));
     const bool two = npairs > pc_one / 2 && pc_one >= 64 && g_opt_lanes.load() != 0;   // cfg3 (1152 pairs, groups of 192): 226 -> 231 k pairs/s
@@ -1270,8 +1250,8 @@ int b4d_phase_correlation(b4d_plan* pl, const float* images, int nimg, const flo
     if ((rc = track_sources(c, ny, nx, ny, nx, true, 2, srcs, roi_part, pidx, st))) return rc;
     if ((rc = forward_spectra_sources(pl, images, nimg, tpl_src, ntpl, srcs, spec, nyq_rows, nyq, st))) return rc;
     // ---- pairs
-    Lanes ln;
-    if ((rc = ln.fork(pl, st, two))) return rc;
+    Lanes ln;   // (joins on the early returns below as well)
+    if ((rc = ln.fork(pl->lanes, st, two))) return rc;
     int grp = 0;
     for (int p0 = 0; p0 < npairs; p0 += pc, ++grp) {
         const int np = std::min(pc, npairs - p0), slot = ln.slot(grp);

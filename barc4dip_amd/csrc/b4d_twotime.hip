@@ -26,6 +26,7 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -87,13 +88,6 @@ static bool tt_layout(int T, long long npix, int R, int L, TTLayout& y) {
     return true;
 }
 
-// the same bits in every lane: lane l and its partner add the same two numbers at every step
-__device__ __forceinline__ double tt_xsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- labels as bytes: 0 outside 1 .. R; without a label map every pixel is region 1.  grid ceil(npix / 256)
 __global__ void __launch_bounds__(256) k_tt_labels(const int* __restrict__ labels, long long npix, int R, uint8_t* __restrict__ lab) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -133,7 +127,7 @@ __global__ void __launch_bounds__(64) k_tt_scan(const float* __restrict__ x, int
                     const bool fin = isfinite(v[u]);
                     if (!fin) allfin = false;
                     const bool use = mine && fin && t + u < t1;
-                    const double s = tt_xsum(use ? (double)v[u] : 0.0);
+                    const double s = wave_sum_all(use ? (double)v[u] : 0.0);
                     const double c = (double)__popcll(__ballot(use));
                     if (lane == u) {
                         ms = s;
@@ -162,8 +156,8 @@ __global__ void __launch_bounds__(64) k_tt_colsum(const double* __restrict__ psu
         a += psum[at];
         if (pcnt) n += pcnt[at];
     }
-    a = tt_xsum(a);
-    if (pcnt) n = tt_xsum(n);
+    a = wave_sum_all(a);
+    if (pcnt) n = wave_sum_all(n);
     if (threadIdx.x == 0) {
         if (pcnt)
             c[rt] = n > 0.0 ? (float)(a / n) : 0.f;
@@ -264,7 +258,7 @@ __global__ void __launch_bounds__(64) k_tt_pack(const float* __restrict__ x, int
                         v = x[(size_t)(t + u) * (size_t)npix + (size_t)p] - c[(size_t)(r - 1) * T + t + u];
                         Xc[(size_t)(t + u) * (size_t)ktot + (size_t)dst] = v;
                     }
-                    const double s = tt_xsum((double)v);
+                    const double s = wave_sum_all((double)v);
                     if (lane == u) ms = s;
                 }
                 if (lane < TT_U && t + lane < t1) psum[((size_t)blockIdx.x * R + (r - 1)) * T + t + lane] += ms;

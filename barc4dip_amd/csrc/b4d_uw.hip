@@ -11,6 +11,7 @@
 // r1, r2: standard normals, either supplied (device pointers: a host stream uploaded by the caller, as the parity tests do) or
 // generated here (Philox-4x32-10 keyed by `seed`, counter = element, sweep; Box-Muller).
 #include "b4d_common.hpp"
+#include "b4d_reduce.hpp"
 
 namespace b4d {
 
@@ -90,11 +91,11 @@ __global__ void __launch_bounds__(256) k_uw_step(UwArgs p) {
     double v[4] = {q1, q2, d1, d2};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
+        v[k] = wave_sum(v[k]);
         if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
     }
     __syncthreads();
+    // (not block_sum_columns of b4d_reduce.hpp: this combine starts from the first wave's sum, not from 0.0)
     if (threadIdx.x < 4) p.part[(size_t)blockIdx.x * 4 + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
 }
 

@@ -289,9 +289,8 @@ extern "C" int b4d_spline_prefilter(const float* src, int n, int h, int w, int m
     hipLaunchKernelGGL(k_prefilter_col, dim3((wp + WP_THREADS - 1) / WP_THREADS, (hp + WP_RB - 1) / WP_RB, n), dim3(WP_THREADS),
                        0, st, src, h, w, pad, mode, coef);
     B4D_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_prefilter_row, dim3(hp, n), dim3(WP_THREADS), sizeof(float) * wp, st, coef, hp, wp, mode);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    // dynamic LDS: one padded row, at most 4 WP_MAX_ROW = 65 536 bytes (the check above): 64 KiB is reached, never passed
+    return launch(k_prefilter_row, dim3(hp, n), dim3(WP_THREADS), sizeof(float) * wp, st, coef, hp, wp, mode);
 }
 
 extern "C" int b4d_warp_dense(const float* src, int n, int h, int w, int order, int mode, float cval, const float* dy,

@@ -19,8 +19,7 @@ namespace b4d {
 __global__ void __launch_bounds__(64) k_absmax_final(float* __restrict__ amax, int nparts) {
     float m = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 64) m = fmaxf(m, amax[i]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
+    m = wave_max(m);
     if (threadIdx.x == 0) amax[0] = m;
 }
 
@@ -73,8 +72,7 @@ __global__ void __launch_bounds__(1024) k_nanabsmax(const float* __restrict__ x,
         take(a.x); take(a.y); take(a.z); take(a.w);
     }
     for (size_t j = 4 * n4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) take(x[j]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -563,6 +561,7 @@ int b4d_richardson_lucy(const float* frames, int batch, int h, int w, const floa
     float* psf = amax + 256;
     B4D_HIP(hipMemcpyAsync(psf, psf_host, sizeof(float) * ky * kx, hipMemcpyHostToDevice, st));
     B4D_HIP(hipStreamSynchronize(st));   // psf_host is caller-owned
+    // dynamic LDS of k_rl_step: the haloed tile and the kernel; at most 4 (96 * 64 + 33 * 33) = 28 932 bytes (ky = kx = RL_MAXK)
     const size_t lds = sizeof(float) * ((size_t)(RL_TX + 2 * px) * (RL_TY + 2 * py) + (size_t)ky * kx);
     const dim3 grid((W + RL_TX - 1) / RL_TX, (H + RL_TY - 1) / RL_TY);
     for (int b = 0; b < batch; ++b) {
@@ -572,8 +571,8 @@ int b4d_richardson_lucy(const float* frames, int batch, int h, int w, const floa
         hipLaunchKernelGGL(k_pad_reflect, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f, h, w, py, px, amax, work);
         hipLaunchKernelGGL(k_fill, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, est, n, 0.5f);
         for (int it = 0; it < num_iter; ++it) {
-            hipLaunchKernelGGL((k_rl_step<0>), grid, dim3(256), lds, st, est, work, rel, psf, H, W, ky, kx, filter_epsilon);
-            hipLaunchKernelGGL((k_rl_step<1>), grid, dim3(256), lds, st, rel, work, est, psf, H, W, ky, kx, 0.f);
+            if ((rc = launch(k_rl_step<0>, grid, dim3(256), lds, st, est, work, rel, psf, H, W, ky, kx, filter_epsilon))) return rc;
+            if ((rc = launch(k_rl_step<1>, grid, dim3(256), lds, st, rel, work, est, psf, H, W, ky, kx, 0.f))) return rc;
         }
         hipLaunchKernelGGL(k_crop_out<float>, dim3((unsigned)((fp + 255) / 256)), dim3(256), 0, st, est, h, w, py, px, amax, clip, out + b * fp);
         B4D_HIP(hipGetLastError());

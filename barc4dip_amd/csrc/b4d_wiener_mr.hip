@@ -174,8 +174,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_fwd(const float* 
             const int m = ln.ltr + r * L;
             if (m < M1) MX::stage1_item(v[r], m, ln.buf, ln.twN);
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_down(mx, o, 64));
+        mx = wave_max(mx);
         if ((ln.tid & 63) == 0) wmax[ln.tid >> 6] = mx;
         __syncthreads();
         if (ln.lt == 0 && act) {
@@ -242,6 +241,7 @@ __global__ void __launch_bounds__(MY::LANES, 4) k_wmr_cols(float2* __restrict__ 
     if (MODE == 0 && k == 0 && tid < 64) {   // max|frame| from the pair maxima of k_wmr_rows_fwd (fmaxf drops NaN: np.nanmax)
         float mx = 0.f;
         for (int i = tid; i < g.hp; i += 64) mx = fmaxf(mx, pmax[(size_t)f * g.hp + i]);
+        // (wave_max of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_down(mx, o, 64));
         if (tid == 0) amax[f] = mx;
@@ -547,6 +547,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
                 low += (mb == mb && kbin(mb) < pred_bin) ? 1u : 0u;
             }
         }
+        // (wave_argmax of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ov = __shfl_down(bv, o, 64);
@@ -554,6 +555,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
             argmax_merge(bv, bi, ov, oi);
         }
         const int lane = tidq & 63, wv = tidq >> 6;
+        // (wave_scan_inclusive and wave_sum of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
         unsigned incl = cnt;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -663,6 +665,7 @@ __global__ void __launch_bounds__(256) k_wmr_peak(const float2* __restrict__ T, 
         const double v = (double)t[(size_t)k * g.Hp].x;
         acc += (k == 0 || 2 * k == g.W) ? v : 2.0 * v;
     }
+    // (wave_sum of b4d_reduce.hpp, kept inline: through the helper this kernel's instructions come out different)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
@@ -845,23 +848,13 @@ static int wmr_cus() {
     return n;
 }
 
-// persistent row kernels: one workgroup per CU when a workgroup needs most of the LDS, as many as fit otherwise.  The dynamic-LDS
-// attribute is set once per (kernel address, device): ensure_dynamic_lds (b4d_common.hpp).
-// (The arguments take the kernel's own parameter types, deduced from `kernel` alone: a mismatch is an error at the call.)
-template <class T>
-struct WmrArg {
-    using type = T;
-};
-template <class MX, class... P>
-static int launch_rows(void (*kernel)(P...), int nquads, hipStream_t st, typename WmrArg<P>::type... args) {
+// persistent row kernels: one workgroup per CU when a workgroup needs most of the LDS, as many as fit otherwise; the rest is
+// launch() (b4d_common.hpp)
+template <class MX, class... P, class... A>
+static int launch_rows(void (*kernel)(P...), int nquads, hipStream_t st, const A&... args) {
     const size_t lds = wmr_rows_lds<MX>();
-    int rc = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds);
-    if (rc) return rc;
     const int per_cu = std::max(1, std::min((int)((size_t)160 * 1024 / lds), 2048 / (WMR_Q * MX::LANES)));
-    const int grid = std::min(nquads, wmr_cus() * per_cu);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WMR_Q * MX::LANES), lds, st, args...);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return launch(kernel, dim3(std::min(nquads, wmr_cus() * per_cu)), dim3(WMR_Q * MX::LANES), lds, st, args...);
 }
 
 // fn(Mix3<...>{}) of the compiled length n: the one expansion of the length table into code
