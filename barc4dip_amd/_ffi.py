@@ -41,6 +41,7 @@ SIGNATURES = {
     "b4d_last_error": (C.c_char_p, []),
     "b4d_set_option": (_i, [C.c_char_p, _i]),
     "b4d_size_supported": (_i, [_i, _i]),
+    "b4d_size_route": (_u, [_i, _i]),
     "b4d_plan_create_general": (_i, [_i, _i, _i, C.POINTER(_vp)]),
     "b4d_fft2d_c2c": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "b4d_plan_create": (_i, [_i, _i, _i, C.POINTER(_vp)]),

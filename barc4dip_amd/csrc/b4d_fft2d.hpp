@@ -1077,6 +1077,7 @@ struct b4d_plan {
     // both sides have in-register three-radix kernels (b4d_wiener_mr.hip): the transform-based entry points take those passes,
     // whatever the size class (228-px aggregator tiles as well as 2560 x 2160 frames); tw_x / tw_y are built for it
     bool wmr = false;
+    unsigned route = 0;        // B4D_ROUTE_* bits of this plan (size_route below): what the entry points branch on
     LaneSync lanes;            // second stream and fork / join events of the two-lane drivers (b4d_lanes.hpp)
 };
 
@@ -1107,6 +1108,15 @@ static inline int col_ct(int ny) {
     return 16;
 }
 static inline bool general_ok(int n) { return n >= 2 && n <= 512; }
+// b4d_general.hip: the one place that decides which kernels a supported (ny, nx) runs.  plan_create_impl fills the plan from it,
+// the entry points branch on the plan's copy, and b4d_size_route reports `bits` (B4D_ROUTE_*, include/b4d.h) without a GPU.
+struct SizeRoute {
+    unsigned bits;
+    bool general;   // a general-length plan: every size that is not power of two on both sides, and every plan of b4d_plan_create_general
+    bool large;     // general, a side beyond the DFT-matrix range: dft2 runs row transforms per axis (the complex entry points of a WMR plan too)
+    bool wmr;
+};
+SizeRoute size_route(int ny, int nx, bool force_general);
 
 static inline int make_twiddles(int n, float2** out) {
     std::vector<float2> h(n);

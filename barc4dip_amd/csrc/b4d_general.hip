@@ -59,6 +59,11 @@ __global__ void __launch_bounds__(256) k_cgemm(GemmArgs g) {
             }
         }
         __syncthreads();
+        float2 part[4][4];   // this tile's 16 terms on their own, then one add: see k_cgemm_mfma
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) part[i][j] = make_float2(0.f, 0.f);
 #pragma unroll
         for (int kk = 0; kk < 16; ++kk) {
             float2 a[4], b[4];
@@ -70,10 +75,17 @@ __global__ void __launch_bounds__(256) k_cgemm(GemmArgs g) {
             for (int i = 0; i < 4; ++i)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    acc[i][j].x = fmaf(a[i].x, b[j].x, fmaf(-a[i].y, b[j].y, acc[i][j].x));
-                    acc[i][j].y = fmaf(a[i].x, b[j].y, fmaf(a[i].y, b[j].x, acc[i][j].y));
+                    part[i][j].x = fmaf(a[i].x, b[j].x, fmaf(-a[i].y, b[j].y, part[i][j].x));
+                    part[i][j].y = fmaf(a[i].x, b[j].y, fmaf(a[i].y, b[j].x, part[i][j].y));
                 }
         }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                acc[i][j].x += part[i][j].x;
+                acc[i][j].y += part[i][j].y;
+            }
         __syncthreads();
     }
 #pragma unroll
@@ -89,6 +101,11 @@ __global__ void __launch_bounds__(256) k_cgemm(GemmArgs g) {
 }
 
 // The same product on the matrix cores: v_mfma_f32_32x32x2_f32 (f32 in, f32 accumulate, bit-for-bit an fmaf chain).
+// The chain is cut every 16 k: each tile of the k loop is summed on its own and added to the running total, so that a sum of K
+// terms rounds 16 + K / 16 times in a row and not K times.  One uncut chain over K = 512 terms of one sign and size -- the ky = 0
+// row of a frame that is constant along y -- drifts by 6e-6 of the result, 1e-5 of its square.
+// The tile sums are a second set of 32 accumulators: left alone the compiler takes 140 registers (3 waves per SIMD, where the
+// uncut kernel ran 5 on 90) and the 500 x 500 transform is 23 % slower; held to 4 waves it takes 114 and costs 4.5 %.
 // 64 x 64 complex tile per workgroup, 4 waves in 2 x 2, each wave a 32 x 32 complex tile = two f32x16 accumulators
 // (re, im); per k-step of 2 one ds_read_b64 per operand feeds four MFMAs:
 //   Cr += Ar*Br - Ai*Bi,  Ci += Ar*Bi + Ai*Br.
@@ -97,7 +114,7 @@ __global__ void __launch_bounds__(256) k_cgemm(GemmArgs g) {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <bool AREAL, bool BREAL>
-__global__ void __launch_bounds__(256) k_cgemm_mfma(GemmArgs g) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_cgemm_mfma(GemmArgs g) {
     __shared__ float2 As[16][65];  // [k][m]
     __shared__ float2 Bs[16][65];  // [k][n]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -124,15 +141,20 @@ __global__ void __launch_bounds__(256) k_cgemm_mfma(GemmArgs g) {
             }
         }
         __syncthreads();
+        f32x16 pr, pi;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) pr[r] = pi[r] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < 16; kk += 2) {
             const float2 a = As[kk + lk][32 * wr + li];
             const float2 b = Bs[kk + lk][32 * wc + li];
-            cr = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, cr, 0, 0, 0);
-            cr = __builtin_amdgcn_mfma_f32_32x32x2f32(-a.y, b.y, cr, 0, 0, 0);
-            ci = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, ci, 0, 0, 0);
-            ci = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, ci, 0, 0, 0);
+            pr = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, pr, 0, 0, 0);
+            pr = __builtin_amdgcn_mfma_f32_32x32x2f32(-a.y, b.y, pr, 0, 0, 0);
+            pi = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, pi, 0, 0, 0);
+            pi = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.x, pi, 0, 0, 0);
         }
+        cr += pr;
+        ci += pi;
         __syncthreads();
     }
     const int n = n0 + 32 * wc + li;
@@ -264,6 +286,27 @@ __global__ void __launch_bounds__(256) k_half_peak(const float2* __restrict__ GT
 
 using namespace b4d;
 
+// Host arithmetic only.  The order of the tests is the order in which general_psd_autocorr and general_fft2d try their routes.
+SizeRoute size_route(int ny, int nx, bool force_general) {
+    SizeRoute r{0u, true, false, false};
+    if (!force_general && pow2_ok(ny) && pow2_ok(nx)) {
+        r.general = false;
+        r.bits = B4D_ROUTE_POW2 | (ny == 2048 ? B4D_ROUTE_PARITY : 0u);
+        return r;
+    }
+    r.large = !(general_ok(ny) && general_ok(nx));
+    r.wmr = wmr_supported(ny) && wmr_supported(nx);
+    if (r.wmr)
+        r.bits = B4D_ROUTE_WMR;
+    else if (!r.large)
+        r.bits = B4D_ROUTE_DFTMAT;
+    else if (pm_fusable(nx) && pm_fusable(ny))
+        r.bits = B4D_ROUTE_FUSED;
+    else
+        r.bits = B4D_ROUTE_PMROWS | (pm_fusable(ny) ? 0u : B4D_ROUTE_BLUESTEIN_Y) | (pm_fusable(nx) ? 0u : B4D_ROUTE_BLUESTEIN_X);
+    return r;
+}
+
 int b4d_cgemm(const void* A, bool a_real, long long sA, int conj_a, const void* B, bool b_real, long long sB, int conj_b,
               float2* C, long long sC, int M, int N, int K, int batch, hipStream_t st) {
     GemmArgs g{A, B, C, M, N, K, sA, sB, sC, conj_a, conj_b};
@@ -323,7 +366,7 @@ int general_psd_autocorr(b4d_plan* pl, const float* frames, int batch, float* ps
                          unsigned flags, hipStream_t st) {
     const int ny = pl->ny, nx = pl->nx, npix = ny * nx;
     const dim3 eg((npix + 255) / 256, 1);
-    if (pl->wmr) {
+    if (pl->route & B4D_ROUTE_WMR) {
         // both sides have in-register three-radix kernels (b4d_wiener_mr.hip): forward row pairs -> transposed half spectra,
         // one pass over the columns (forward, |F|^2, inverse; the column stays in LDS), inverse row pairs + PSD rows:
         // 3 passes and ~32 bytes per pixel where the route below makes 7 passes
@@ -343,7 +386,7 @@ int general_psd_autocorr(b4d_plan* pl, const float* frames, int batch, float* ps
         }
         return ln.close();
     }
-    if (pl->large && pm_fusable(nx) && pm_fusable(ny)) {
+    if (pl->route & B4D_ROUTE_FUSED) {
         // half-spectrum path: pair rows -> transpose -> columns on nx/2 + 1 sequences -> |F|^2 (+ PSD) -> inverse columns ->
         // transpose -> Hermitian pair rows written fftshift-ed and normalised: ~56 instead of ~148 bytes per pixel
         const int Wh = nx / 2 + 1;
@@ -390,7 +433,7 @@ int general_psd_autocorr(b4d_plan* pl, const float* frames, int batch, float* ps
 
 int general_fft2d(b4d_plan* pl, const float* frames, int batch, float2* out, hipStream_t st) {
     const int ny = pl->ny, nx = pl->nx, npix = ny * nx;
-    if (pl->wmr) {   // mixed-radix kernels on both sides (b4d_wiener_mr.hip)
+    if (pl->route & B4D_ROUTE_WMR) {   // mixed-radix kernels on both sides (b4d_wiener_mr.hip)
         // two-lane launch groups (Lanes, b4d_lanes.hpp): lane l works in gbuf(1 + l)
         const size_t selems = wmr_spectrum_elems(ny, nx);
         Lanes ln;

@@ -94,6 +94,7 @@ static bool large_ok(int ny, int nx) {
 int b4d_size_supported(int ny, int nx) {
     return (pow2_ok(ny) && pow2_ok(nx)) || (general_ok(ny) && general_ok(nx)) || large_ok(ny, nx);
 }
+unsigned b4d_size_route(int ny, int nx) { return b4d_size_supported(ny, nx) ? size_route(ny, nx, false).bits : 0u; }
 
 static int plan_create_impl(int ny, int nx, int chunk, bool force_general, b4d_plan** out);
 int b4d_plan_create(int ny, int nx, int chunk, b4d_plan** out) { return plan_create_impl(ny, nx, chunk, false, out); }
@@ -118,10 +119,12 @@ static int plan_create_impl(int ny, int nx, int chunk, bool force_general, b4d_p
     p->ny = ny;
     p->nx = nx;
     p->chunk = chunk;
-    if (force_general || !(pow2_ok(ny) && pow2_ok(nx))) {  // general-length plan
-        p->general = true;
-        p->large = !(general_ok(ny) && general_ok(nx));
-        p->wmr = wmr_supported(ny) && wmr_supported(nx);
+    const SizeRoute sr = size_route(ny, nx, force_general);
+    p->route = sr.bits;
+    p->general = sr.general;
+    p->large = sr.large;
+    p->wmr = sr.wmr;
+    if (p->general) {
         int rc = B4D_OK;
         if (p->wmr && !p->large) {   // small frames on the mixed-radix passes keep their DFT matrices for the complex entry points
             rc = make_twiddles(nx, &p->tw_x);
@@ -156,7 +159,7 @@ static int plan_create_impl(int ny, int nx, int chunk, bool force_general, b4d_p
     p->ct_w = col_ct(ny);
     int rc = make_twiddles(nx, &p->tw_x);
     if (rc == B4D_OK) rc = make_twiddles(ny, &p->tw_y);
-    if (rc == B4D_OK && ny == 2048) rc = make_twiddles(ny / 2, &p->tw_yh);
+    if (rc == B4D_OK && (p->route & B4D_ROUTE_PARITY)) rc = make_twiddles(ny / 2, &p->tw_yh);
     if (rc != B4D_OK) {
         b4d_plan_destroy(p);
         return rc;
@@ -221,7 +224,7 @@ static int psd_autocorr_impl(b4d_plan* pl, const float* frames, int batch, float
     const size_t fpix = (size_t)pl->ny * pl->nx;
     // one route per call, chosen by the frame shape alone (never by batch, chunk or lanes): 2048-row frames take the parity-tile
     // route, where the row passes do one radix-2 stage of the column transform
-    const bool parity = pl->ny == 2048 && pl->tw_yh && g_opt_ysplit.load();
+    const bool parity = (pl->route & B4D_ROUTE_PARITY) && pl->tw_yh && g_opt_ysplit.load();
     // column-set tiles need two row transforms per workgroup of the forward row pass: every nx but 4096
     const Route rt = parity ? Route{true, ColCfg<1024, 1>::CT, pl->tw_yh, g_opt_row16.load(), pl->nx <= 2048 ? g_opt_colsets.load() : 0}
                             : Route{false, pl->ct_w, pl->tw_y, 0, 0};

@@ -76,6 +76,18 @@ int b4d_set_option(const char* name, int value);
  * sides <= 8192 that split as 2^k * A * B with A + B <= 128 (fused in-LDS mixed radix) or any other side <= 4096
  * (Bluestein over that transform), at most 2^26 pixels. */
 int b4d_size_supported(int ny, int nx);
+/* Which kernels a plan from b4d_plan_create runs for (ny, nx), as flag bits; 0 for a size without a plan.  No GPU call: the plan
+ * constructor and the entry points branch on the same bits, so a test can assert the route of a shape where it cannot run it.
+ * Exactly one of POW2, WMR, FUSED, DFTMAT and PMROWS is set for a supported size. */
+#define B4D_ROUTE_POW2 0x01u        /* power-of-two pipeline: radix FFT kernels, half spectrum between row and column pass */
+#define B4D_ROUTE_PARITY 0x02u      /* ny == 2048: PSD + autocorrelation can take the parity tiles (options ysplit, row16, colsets) */
+#define B4D_ROUTE_WMR 0x04u         /* both sides have compiled three-radix kernels: the three-kernel mixed-radix route */
+#define B4D_ROUTE_FUSED 0x08u       /* a side beyond 512, both sides split as 2^k * A * B: fused half-spectrum route */
+#define B4D_ROUTE_DFTMAT 0x10u      /* both sides <= 512: DFT-matrix products */
+#define B4D_ROUTE_PMROWS 0x20u      /* a side beyond 512 and a side without such a split: full complex row transforms per axis */
+#define B4D_ROUTE_BLUESTEIN_Y 0x40u /* (with PMROWS) ny has no 2^k * A * B split: its transforms run through Bluestein */
+#define B4D_ROUTE_BLUESTEIN_X 0x80u /* the same for nx */
+unsigned b4d_size_route(int ny, int nx);
 
 /* Plans ------------------------------------------------------------------------------
  * A plan owns the twiddle tables and a workspace of `chunk` half-spectra
