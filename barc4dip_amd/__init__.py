@@ -5,7 +5,7 @@ kernels through the C ABI declared in include/b4d.h.  There is no CPU fallback.
 """
 from __future__ import annotations
 
-__version__ = "0.3.0"
+__version__ = "0.4.0"
 
 from . import geometry, maths, metrics, preprocessing, signal, utils  # noqa: F401
 from .metrics import (distribution_moments, sharpness_stack_stats, sharpness_stats, speckle_stack_stats,  # noqa: F401

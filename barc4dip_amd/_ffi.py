@@ -116,6 +116,9 @@ SIGNATURES = {
     "b4d_rank_filter": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "b4d_despeckle": (_i, [_vp, _i, _i, _i, _i, _i, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp]),
     "b4d_scale_to_u16": (_i, [_vp, _sz, _f, _d, _i, _vp, _vp]),
+    "b4d_stepping_fit": (_i, [_vp, _i, _i, C.c_longlong, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    "b4d_stepping_compare": (_i, [_vp, _vp, C.c_longlong, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "b4d_stepping_calibrate_step": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _vp, _d, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

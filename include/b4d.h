@@ -671,6 +671,41 @@ int b4d_despeckle(const float* in, int batch, int ny, int nx, int size, int scal
                   int mode, float cval, float* out, unsigned char* mask, long long* counts, void* stream);
 int b4d_scale_to_u16(const float* in, size_t n, float vmin, double inv, int mul_f64, unsigned short* out, void* stream);
 
+/* Phase-stepping analysis of grating scans (barc4dip_amd.signal.stepping).  A scan is (T, npix) float32, a
+ * stack of scans (n, T, npix).  Per pixel, with step phases phi_t and K = harmonics in {1, 2}, M = 2K + 1:
+ *   I_t = a0 + sum_k (c_k cos k phi_t + s_k sin k phi_t),   a_k = hypot(c_k, s_k),   phi_k = atan2(-s_k, c_k).
+ * basis: HOST (T, M) float64, row t = (1, cos phi_t, sin phi_t, cos 2 phi_t, sin 2 phi_t); gram: HOST (M, M) = basis^T basis;
+ * gram_inv: HOST (M, M), its inverse, or NULL if it has none (every pixel then takes the per-pixel solve).  A sample is dropped
+ * for its pixel if it is not finite or >= saturation (+inf: no level).  A pixel without a dropped sample gets gram_inv b with
+ * b = sum_t B_t I_t; one with dropped samples is solved by Cholesky of gram - sum_dropped B_t B_t^T.  It is valid if at least M
+ * samples are kept and every pivot exceeds 1e-10 times the largest diagonal entry; otherwise its coefficients and residual are
+ * NaN.  All sums are float64, in the order of t.
+ * b4d_stepping_fit: coeff DEVICE (n, M, npix) float32 in the order (a0, c_1, s_1, c_2, s_2); residual DEVICE (n, npix) float32,
+ *   sqrt(max(sum I^2 - b^T x, 0) / n_kept); n_samples DEVICE (n, npix) bytes, the kept samples.  3 <= T <= 64 (B4D_ESIZE),
+ *   T >= M.  16-byte accesses where npix is a multiple of 4 and stack, coeff, residual are 16-byte aligned (n_samples 4-byte),
+ *   dword accesses otherwise; the results are the same bits.
+ * b4d_stepping_compare: elementwise on coefficient maps.  With reference (DEVICE (M, npix) and reference_stride 0, or
+ *   (n, M, npix) and reference_stride M * npix): phase = wrap_(-pi, pi](phi_k,s - phi_k,r) formed in float64, visibility and
+ *   visibility_ref = a_k / a0 of sample and reference, dark_field their quotient (all (n, K, npix) float32), transmission =
+ *   a0_s / a0_r (n, npix), valid (n, K, npix) bytes = both pixels valid, both a0 > 0 and a_k,r > 0; amplitude (sample) optional.
+ *   Without reference (NULL): phase = phi_k, visibility and amplitude of the sample; valid (optional) = the pixel is valid;
+ *   transmission, visibility_ref, dark_field must be NULL.
+ * b4d_stepping_calibrate_step: one iteration of the step self-calibration (K = 1, 5 <= T <= 32) on one scan: one pass over the
+ *   stack fits (a0, c, s) with basis / gram_inv (HOST, formed from the current steps delta, HOST (T)), sums over the pixels
+ *   without a dropped sample the products a0 I_t, c I_t, s I_t and the 3 x 3 matrix of (a0, c, s), and one workgroup solves
+ *   I_t(p) ~ g_t a0(p) + u_t c(p) + v_t s(p) and sets delta_t <- atan2(v_t, u_t) - atan2(v_0, u_0), unwrapped towards the
+ *   previous delta_t.  out: DEVICE 1 + 3 T float64: max |change|, the new delta (T), the dose factors g (T), the modulations
+ *   hypot(u, v) (T); NaN throughout if no pixel takes part.  Works in the library's per-stream scratch buffer.
+ * No float atomics, every cross-lane and cross-workgroup sum in a fixed order: the same bits from run to run.  Asynchronous on
+ * `stream`, no host synchronisation; all argument errors are returned before any launch.                                    */
+int b4d_stepping_fit(const float* stack, int n, int T, long long npix, int harmonics, const double* basis, const double* gram,
+                     const double* gram_inv, double saturation, float* coeff, float* residual, unsigned char* n_samples, void* stream);
+int b4d_stepping_compare(const float* sample, const float* reference, long long reference_stride, int n, int harmonics, long long npix,
+                         float* phase, float* visibility, float* amplitude, float* transmission, float* visibility_ref,
+                         float* dark_field, unsigned char* valid, void* stream);
+int b4d_stepping_calibrate_step(const float* stack, int T, long long npix, const double* basis, const double* gram_inv,
+                                const double* delta, double saturation, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
