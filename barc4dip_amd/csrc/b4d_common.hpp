@@ -16,6 +16,8 @@ inline int fail(int code, const std::string& msg) {
     last_error() = msg;
     return code;
 }
+// workspace carving: sizes rounded up to 256 bytes
+inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 // lazily grown device scratch for second-stage reductions (b4d_stats.hip), one buffer per caller stream
 int get_scratch(size_t bytes, void** out, hipStream_t stream);
 // serialises the host side of every entry point that works in a scratch buffer (re-entrant calls from several host

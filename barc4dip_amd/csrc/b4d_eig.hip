@@ -22,13 +22,12 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_mfma.hpp"
 #include "b4d_reduce.hpp"
 
 namespace b4d {
 
 constexpr int NB = 32;  // subspace width
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- 1. normalisation: part[b][blk] = {sum x, sum x^2, n_nonfinite}; grid (nblk, batch), block 1024
 __global__ void __launch_bounds__(1024) k_sta2_sums(const float* __restrict__ x, size_t npix, double* __restrict__ part) {
@@ -106,22 +105,16 @@ struct GramArgs {
 };
 
 // grid (ceil(m/128), ceil(m/128), batch), block 256 = 4 waves in 2 x 2, each a 64 x 64 tile (4 f32x16 accumulators);
-// K staged 32 deep through LDS
+// K staged 32 deep through LDS (multiply and lane maps: b4d_mfma.hpp)
 __global__ void __launch_bounds__(256) k_gram_mfma(GramArgs g) {
     if (blockIdx.x < blockIdx.y) return;
     __shared__ float As[32][129];
     __shared__ float Bs[32][129];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1, li = lane & 31, lk = lane >> 5;
+    const WaveTile t = wave_tile(threadIdx.x);
     const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
     const float* J = g.J + (long long)blockIdx.z * g.bJ;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+    zero(acc);
     const bool kc = g.sk == 1;  // k contiguous in memory
     for (int k0 = 0; k0 < g.K; k0 += 32) {
 #pragma unroll
@@ -135,33 +128,17 @@ __global__ void __launch_bounds__(256) k_gram_mfma(GramArgs g) {
             Bs[kk][xx] = (ib < g.m && k < g.K) ? J[ib * g.si + k * g.sk] : 0.f;
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < 32; kk += 2) {
-            const float a0 = As[kk + lk][64 * wr + li], a1 = As[kk + lk][64 * wr + 32 + li];
-            const float b0 = Bs[kk + lk][64 * wc + li], b1 = Bs[kk + lk][64 * wc + 32 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        mma_slab<32>(As, Bs, t, acc);
         __syncthreads();
     }
     float* G = g.G + (long long)blockIdx.z * g.bG;
     const bool mirror = blockIdx.x != blockIdx.y;
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int n = n0 + 64 * wc + 32 * b + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mm = m0 + 64 * wr + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (mm < g.m && n < g.m) {
-                    G[(long long)mm * g.m + n] = acc[a][b][r];
-                    if (mirror) G[(long long)n * g.m + mm] = acc[a][b][r];
-                }
-            }
+    for_each(acc, t, m0, n0, [&](int mm, int n, float v) {
+        if (mm < g.m && n < g.m) {
+            G[(long long)mm * g.m + n] = v;
+            if (mirror) G[(long long)n * g.m + mm] = v;
         }
+    });
 }
 
 // ---- 3. W = G V for symmetric G (m x m) and a block V (m x NB): every wave streams its K slice of a 32-row slab of G
@@ -180,8 +157,7 @@ __global__ void __launch_bounds__(SYMM_WAVES * 64) k_symm_block(const float* __r
     kc = (kc + 1) & ~1;
     const int kbeg = min(m, wave * kc), kend = min(m, kbeg + kc);
     f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    zero(acc);
     int k = kbeg;
     for (; k + 16 <= kend; k += 16) {
         float a[8], b[8];
@@ -202,17 +178,17 @@ __global__ void __launch_bounds__(SYMM_WAVES * 64) k_symm_block(const float* __r
     // waves 8..15 hand their tiles to waves 0..7, then the 8 survivors are summed by all lanes
     if (wave >= SYMM_WAVES / 2) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave - SYMM_WAVES / 2][(r & 3) + 8 * (r >> 2) + 4 * lk][li] = acc[r];
+        for (int r = 0; r < 16; ++r) red[wave - SYMM_WAVES / 2][mfma_row(r, lk)][mfma_col(li)] = acc[r];
     }
     __syncthreads();
     if (wave < SYMM_WAVES / 2) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] += red[wave][(r & 3) + 8 * (r >> 2) + 4 * lk][li];
+        for (int r = 0; r < 16; ++r) acc[r] += red[wave][mfma_row(r, lk)][mfma_col(li)];
     }
     __syncthreads();
     if (wave < SYMM_WAVES / 2) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) red[wave][(r & 3) + 8 * (r >> 2) + 4 * lk][li] = acc[r];
+        for (int r = 0; r < 16; ++r) red[wave][mfma_row(r, lk)][mfma_col(li)] = acc[r];
     }
     __syncthreads();
     const int row = threadIdx.x / NB, col = threadIdx.x % NB;

@@ -358,8 +358,6 @@ __global__ void __launch_bounds__(256) k_focus_fin(FinArgs a) {
     }
 }
 
-static size_t focus_up(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // workspace layout (byte offsets, 256-byte aligned parts)
 struct FocusWs {
     size_t z, asum, prm, rowsum, rowq, colpart, peakv, peaki, total;
@@ -370,14 +368,14 @@ static FocusWs focus_layout(const b4d_plan* pl, int n, int nz) {
     const size_t Py = pl->ny, Px = pl->nx, ch = pl->chunk;
     w.nbands = (int)((Py + FOCUS_BAND - 1) / FOCUS_BAND);
     size_t o = 0;
-    w.z = o, o += focus_up(sizeof(double) * (size_t)nz);
-    w.asum = o, o += focus_up(sizeof(double) * 2 * (size_t)n);
-    w.prm = o, o += focus_up(sizeof(double) * FOCUS_PRM * (size_t)n * nz);
-    w.rowsum = o, o += focus_up(sizeof(double) * ch * Py);
-    w.rowq = o, o += focus_up(sizeof(double) * ch * Py);
-    w.colpart = o, o += focus_up(sizeof(double) * ch * w.nbands * Px);
-    w.peakv = o, o += focus_up(sizeof(double) * ch * w.nbands);
-    w.peaki = o, o += focus_up(sizeof(int) * ch * w.nbands);
+    w.z = o, o += align256(sizeof(double) * (size_t)nz);
+    w.asum = o, o += align256(sizeof(double) * 2 * (size_t)n);
+    w.prm = o, o += align256(sizeof(double) * FOCUS_PRM * (size_t)n * nz);
+    w.rowsum = o, o += align256(sizeof(double) * ch * Py);
+    w.rowq = o, o += align256(sizeof(double) * ch * Py);
+    w.colpart = o, o += align256(sizeof(double) * ch * w.nbands * Px);
+    w.peakv = o, o += align256(sizeof(double) * ch * w.nbands);
+    w.peaki = o, o += align256(sizeof(int) * ch * w.nbands);
     w.total = o;
     return w;
 }

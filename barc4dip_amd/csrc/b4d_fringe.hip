@@ -39,14 +39,12 @@ struct FrTables {
     float2* ex;       // (K, W)   exp(-2 pi i fx x)
 };
 
-static size_t fr_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 static size_t fr_layout(char* base, int K, int H, int W, int wy, int wx, FrTables& t) {
     size_t o = 0;
-    t.hy = (float*)(base + o), o += fr_align256((size_t)wy * sizeof(float));
-    t.hx = (float*)(base + o), o += fr_align256((size_t)wx * sizeof(float));
-    t.ey = (float2*)(base + o), o += fr_align256((size_t)K * H * sizeof(float2));
-    t.ex = (float2*)(base + o), o += fr_align256((size_t)K * W * sizeof(float2));
+    t.hy = (float*)(base + o), o += align256((size_t)wy * sizeof(float));
+    t.hx = (float*)(base + o), o += align256((size_t)wx * sizeof(float));
+    t.ey = (float2*)(base + o), o += align256((size_t)K * H * sizeof(float2));
+    t.ex = (float2*)(base + o), o += align256((size_t)K * W * sizeof(float2));
     return o;
 }
 
@@ -413,7 +411,7 @@ extern "C" int b4d_fringe_compare(const void* sample, const void* reference, lon
 
 extern "C" size_t b4d_fringe_weights_workspace_bytes(int n, int gy, int gx) {
     if (n < 1 || n > 65535 || gy < 1 || gx < 1 || (long long)gy * gx > (1LL << 28)) return 0;
-    return 2 * fr_align256((size_t)n * fr_w_blocks((long long)gy * gx) * sizeof(float));
+    return 2 * align256((size_t)n * fr_w_blocks((long long)gy * gx) * sizeof(float));
 }
 
 extern "C" int b4d_fringe_weights(const void* sample, const void* reference, long long reference_stride, int n, int n_carriers, int gy,
@@ -434,7 +432,7 @@ extern "C" int b4d_fringe_weights(const void* sample, const void* reference, lon
     hipStream_t st = (hipStream_t)stream;
     const int nb = fr_w_blocks(plane);
     float* part_s = (float*)workspace;
-    float* part_r = (float*)((char*)workspace + fr_align256((size_t)n * nb * sizeof(float)));
+    float* part_r = (float*)((char*)workspace + align256((size_t)n * nb * sizeof(float)));
     if (min_level > 0.0)
         hipLaunchKernelGGL(k_fr_level_partials, dim3(nb, n, reference ? 2 : 1), dim3(FR_W_THREADS), 0, st, (const float2*)sample,
                            (const float2*)reference, reference_stride ? n : 1, (n_carriers + 1) * plane, (int)plane, nb, part_s, part_r);

@@ -6,9 +6,10 @@
 // small, awkward lengths the 2-D DFT is evaluated as F = Wy * X * Wx with precomputed DFT matrices: a genuinely
 // dense contraction (the one place on this path where that appears), regular, any length, float32-exact FMA
 // chains.  O(n^3) per transform keeps it to n <= 512; power-of-two frames never come here (b4d_fft2d.hpp).
-// The product kernel is a plain LDS-tiled complex GEMM on the vector ALUs (64x64 tile, 4x4 register block);
-// moving it to v_mfma_f32_32x32x2_f32 is listed in DESIGN.md §8.
+// The product kernel is an LDS-tiled complex GEMM on the matrix cores (k_cgemm_mfma: v_mfma_f32_32x32x2_f32, 64x64 tile);
+// k_cgemm, the same product on the vector ALUs, is kept as the B4D_CGEMM_VALU reference of tools/dev_ab.py.
 #include "b4d_fft2d.hpp"
+#include "b4d_mfma.hpp"
 #include "b4d_pm.hpp"
 #include "b4d_wiener_mr.hpp"
 
@@ -108,23 +109,17 @@ __global__ void __launch_bounds__(256) k_cgemm(GemmArgs g) {
 // uncut kernel ran 5 on 90) and the 500 x 500 transform is 23 % slower; held to 4 waves it takes 114 and costs 4.5 %.
 // 64 x 64 complex tile per workgroup, 4 waves in 2 x 2, each wave a 32 x 32 complex tile = two f32x16 accumulators
 // (re, im); per k-step of 2 one ds_read_b64 per operand feeds four MFMAs:
-//   Cr += Ar*Br - Ai*Bi,  Ci += Ar*Bi + Ai*Br.
-// Fragment maps (MI355X guide §3): A: lane l holds A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31];
-// C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
+//   Cr += Ar*Br - Ai*Bi,  Ci += Ar*Bi + Ai*Br.  Lane maps: b4d_mfma.hpp.
 template <bool AREAL, bool BREAL>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k_cgemm_mfma(GemmArgs g) {
     __shared__ float2 As[16][65];  // [k][m]
     __shared__ float2 Bs[16][65];  // [k][n]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
+    const WaveTile t = wave_tile(threadIdx.x);
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     const long long oa = (long long)blockIdx.z * g.sA, ob = (long long)blockIdx.z * g.sB, oc = (long long)blockIdx.z * g.sC;
     f32x16 cr, ci;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cr[r] = ci[r] = 0.f;
-    const int li = lane & 31, lk = lane >> 5;
+    zero(cr);
+    zero(ci);
     for (int k0 = 0; k0 < g.K; k0 += 16) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -142,12 +137,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         }
         __syncthreads();
         f32x16 pr, pi;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) pr[r] = pi[r] = 0.f;
+        zero(pr);
+        zero(pi);
 #pragma unroll
         for (int kk = 0; kk < 16; kk += 2) {
-            const float2 a = As[kk + lk][32 * wr + li];
-            const float2 b = Bs[kk + lk][32 * wc + li];
+            const float2 a = As[kk + t.lk][32 * t.wr + t.li];
+            const float2 b = Bs[kk + t.lk][32 * t.wc + t.li];
             pr = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, pr, 0, 0, 0);
             pr = __builtin_amdgcn_mfma_f32_32x32x2f32(-a.y, b.y, pr, 0, 0, 0);
             pi = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.y, pi, 0, 0, 0);
@@ -157,11 +152,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) k
         ci += pi;
         __syncthreads();
     }
-    const int n = n0 + 32 * wc + li;
+    const int n = n0 + 32 * t.wc + mfma_col(t.li);
     if (n < g.N) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int m = m0 + 32 * wr + (r & 3) + 8 * (r >> 2) + 4 * lk;
+            const int m = m0 + 32 * t.wr + mfma_row(r, t.lk);
             if (m < g.M) g.C[oc + (long long)m * g.N + n] = make_float2(cr[r], ci[r]);
         }
     }

@@ -1,6 +1,6 @@
-// b4d_integrate.hip -- wavefront reconstruction: least-squares integration of a slope field on a regular grid and the
-// low-order (6-term quadratic) fit of the result; the weighted variants (section 14) and the phase unwraps
-// that share their solvers (sections 17 and 18).
+// b4d_integrate.hip -- wavefront reconstruction: least-squares integration of a slope field on a regular grid (DESIGN.md
+// section 13): the product kernel, the DCT basis cache and the Poisson solve; the weighted variant by preconditioned conjugate
+// gradients (section 14) and the two phase unwraps that share these solvers (sections 17 and 18); the fit: b4d_poly2.hip.
 //
 // Southwell geometry: the slope on the edge between two neighbouring nodes is the mean of the two node slopes; phi is the
 // zero-mean minimiser of the squared edge residuals.  The normal equations are a 5-point Neumann Laplacian, which the
@@ -20,16 +20,15 @@
 #include <vector>
 
 #include "b4d_common.hpp"
+#include "b4d_mfma.hpp"
 #include "b4d_reduce.hpp"
+#include "b4d_wf.hpp"
 
 namespace b4d {
 
-constexpr int WF_MAX_SIDE = 2048;
 constexpr int WF_TILE = 128;   // output tile of a workgroup (4 waves in 2 x 2, each 2 x 2 MFMA tiles of 32 x 32)
 constexpr int WF_BK = 16;
 constexpr int WF_LD = 130;     // LDS row stride: 130 % 32 == 2 keeps the staging writes (k fastest) off each other's banks
-
-typedef float wf_f32x16 __attribute__((ext_vector_type(16)));
 
 // ---- right-hand side.  With gbar the edge means, r[i][j] = (gbar_y[i-1][j] - gbar_y[i][j]) / hy + (gbar_x[i][j-1] - gbar_x[i][j]) / hx,
 // terms with an index outside the grid absent: interior (g[i-1] - g[i+1]) / 2, first node -(g[0] + g[1]) / 2, last node
@@ -51,8 +50,7 @@ __global__ void __launch_bounds__(256) k_wf_rhs(const float* __restrict__ gy, co
 }
 
 // ---- real matrix product C[z] = A[z] . B[z] on the matrix cores, row-major operands, batch on blockIdx.z (a stride of 0
-// shares an operand).  K and the M / N edges are padded with zeros in LDS.  Fragment maps of v_mfma_f32_32x32x2_f32:
-// A: lane l holds A[i = l & 31][k = l >> 5], B[k = l >> 5][j = l & 31]; C/D: col = l & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
+// shares an operand).  K and the M / N edges are padded with zeros in LDS; multiply and lane maps: b4d_mfma.hpp.
 // DIV: the store divides by the float32 rounding of the float64 eigenvalue Lambda[m][n] = ly[m] ihy2 + lx[n] ihx2 and zeroes (0, 0).
 struct WfGemm {
     const float* A;
@@ -70,21 +68,14 @@ template <bool DIV>
 __global__ void __launch_bounds__(256) k_wf_gemm(WfGemm g) {
     __shared__ float As[WF_BK][WF_LD];  // [k][m]
     __shared__ float Bs[WF_BK][WF_LD];  // [k][n]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1;
-    const int li = lane & 31, lk = lane >> 5;
+    const WaveTile t = wave_tile(threadIdx.x);
     const int m0 = blockIdx.y * WF_TILE, n0 = blockIdx.x * WF_TILE;
     if (g.skip && g.skip[blockIdx.z]) return;
     const float* __restrict__ A = g.A + (long long)blockIdx.z * g.sA;
     const float* __restrict__ B = g.B + (long long)blockIdx.z * g.sB;
     float* __restrict__ Cm = g.C + (long long)blockIdx.z * g.sC;
-    wf_f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    f32x16 acc[2][2];
+    zero(acc);
     for (int k0 = 0; k0 < g.K; k0 += WF_BK) {
 #pragma unroll
         for (int r = 0; r < WF_TILE * WF_BK / 256; ++r) {
@@ -101,96 +92,20 @@ __global__ void __launch_bounds__(256) k_wf_gemm(WfGemm g) {
             }
         }
         __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < WF_BK; kk += 2) {
-            const float a0 = As[kk + lk][64 * wr + li], a1 = As[kk + lk][64 * wr + 32 + li];
-            const float b0 = Bs[kk + lk][64 * wc + li], b1 = Bs[kk + lk][64 * wc + 32 + li];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        mma_slab<WF_BK>(As, Bs, t, acc);
         __syncthreads();
     }
+    double lxn[2] = {0.0, 0.0};   // the x term of Lambda for the lane's two columns (32 apart), once per column
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int n = n0 + 64 * wc + 32 * j + li;
-        if (n >= g.N) continue;
-        double lxn = 0.0;
-        if (DIV) lxn = g.lx[n] * g.ihx2;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int m = m0 + 64 * wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                if (m >= g.M) continue;
-                float v = acc[i][j][r];
-                if (DIV) v = (m == 0 && n == 0) ? 0.f : v / (float)(g.ly[m] * g.ihy2 + lxn);
-                Cm[(long long)m * g.N + n] = v;
-            }
+    for (int j = 0; DIV && j < 2; ++j) {
+        const int n = n0 + 64 * t.wc + 32 * j + t.li;
+        if (n < g.N) lxn[j] = g.lx[n] * g.ihx2;
     }
-}
-
-// ---- low-order fit: moments sum m_k w of the six monomials m = (1, u, v, u^2, u v, v^2) in float64, u = (j - cx) / xh along x,
-// v = (i - cy) / yh along y; lane 0 multiplies by the inverse Gram matrix of the grid (host, float64).  One workgroup per map.
-struct WfFit {
-    double ginv[36];
-    double cx, cy, ixh, iyh;
-};
-constexpr int WF_FIT_THREADS = 1024;
-
-__global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_moments(const float* __restrict__ w, int ny, int nx, WfFit f,
-                                                                     double* __restrict__ coeff) {
-    __shared__ double sh[WF_FIT_THREADS / 64][6];
-    const int npix = ny * nx;
-    const float* __restrict__ p = w + (size_t)blockIdx.x * npix;
-    double s[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int e = threadIdx.x; e < npix; e += WF_FIT_THREADS) {
-        const int i = e / nx, j = e % nx;
-        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh, x = (double)p[e];
-        s[0] += x;
-        s[1] += u * x;
-        s[2] += v * x;
-        s[3] += u * u * x;
-        s[4] += u * v * x;
-        s[5] += v * v * x;
-    }
-    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
-    if (threadIdx.x == 0)
-        for (int a = 0; a < 6; ++a) {
-            double c = 0.0;
-            for (int b = 0; b < 6; ++b) c += f.ginv[6 * a + b] * s[b];
-            coeff[6 * (size_t)blockIdx.x + a] = c;
-        }
-}
-
-// residual = scale (w - sum of the terms selected by mask) in float32 (may alias w), rms = population standard deviation of
-// the residual in float64
-__global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_residual(const float* w, int ny, int nx, WfFit f,
-                                                                      const double* __restrict__ coeff, unsigned mask, double scale,
-                                                                      float* residual, double* __restrict__ rms) {
-    __shared__ double sh[WF_FIT_THREADS / 64][2];
-    const int npix = ny * nx;
-    const float* p = w + (size_t)blockIdx.x * npix;
-    float* q = residual + (size_t)blockIdx.x * npix;
-    double c[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] = ((mask >> k) & 1u) ? coeff[6 * (size_t)blockIdx.x + k] : 0.0;
-    double s[2] = {0.0, 0.0};
-    for (int e = threadIdx.x; e < npix; e += WF_FIT_THREADS) {
-        const int i = e / nx, j = e % nx;
-        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh;
-        const double fit = c[0] + u * (c[1] + c[3] * u + c[4] * v) + v * (c[2] + c[5] * v);
-        const float out = (float)(scale * ((double)p[e] - fit));
-        q[e] = out;
-        s[0] += (double)out;
-        s[1] += (double)out * (double)out;
-    }
-    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
-    if (threadIdx.x == 0) {
-        const double mean = s[0] / npix;
-        rms[blockIdx.x] = sqrt(fmax(0.0, s[1] / npix - mean * mean));
-    }
+    for_each(acc, t, m0, n0, [&](int m, int n, float v) {
+        if (m >= g.M || n >= g.N) return;
+        if (DIV) v = (m == 0 && n == 0) ? 0.f : v / (float)(g.ly[m] * g.ihy2 + (((n - n0) & 32) ? lxn[1] : lxn[0]));
+        Cm[(long long)m * g.N + n] = v;
+    });
 }
 
 // ---- DCT-II basis C[k][j] = s_k sqrt(2/n) cos(pi (2j+1) k / 2n) (s_0 = 1/sqrt 2), its transpose and the eigenvalue terms
@@ -276,101 +191,6 @@ static int wf_basis(int n, int keep, const WfBasis** out) {
     return B4D_OK;
 }
 
-static int wf_check_grid(int n, int ny, int nx) {
-    if (n < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "map count and sides must be >= 1");
-    if (ny > WF_MAX_SIDE || nx > WF_MAX_SIDE)
-        return fail(B4D_ESIZE, "wavefront grids are limited to " + std::to_string(WF_MAX_SIDE) + " nodes per side, got (" +
-                                   std::to_string(ny) + ", " + std::to_string(nx) + ")");
-    if (n > 65535) return fail(B4D_ESIZE, "at most 65535 maps per call");
-    return B4D_OK;
-}
-
-// Cholesky factor of the Gram matrix G of the six monomials and the solve with it, float64, for the host (unweighted fit: G
-// depends on the grid alone, the host keeps its inverse) and for one lane of the device (weighted fit: G from the weighted
-// moments of the map).  Monomials are taken in order; one whose remainder after the kept ones is below 1e-12 of itself is
-// dropped, and its coefficient is 0.
-struct WfChol {       // the device keeps it in LDS: the loops index it with run-time subscripts
-    double L[6][6];
-    double y[6];
-    bool kept[6];
-};
-
-__host__ __device__ inline void wf_gram_factor(const double (&G)[6][6], WfChol& f) {
-    for (int a = 0; a < 6; ++a) {
-        double d = G[a][a];
-        for (int b = 0; b < a; ++b) {
-            f.L[a][b] = 0.0;
-            if (!f.kept[b]) continue;
-            double s = G[a][b];
-            for (int c = 0; c < b; ++c)
-                if (f.kept[c]) s -= f.L[a][c] * f.L[b][c];
-            f.L[a][b] = s / f.L[b][b];
-            d -= f.L[a][b] * f.L[a][b];
-        }
-        f.kept[a] = d > 1e-12 * G[a][a] && G[a][a] > 0.0;
-        f.L[a][a] = f.kept[a] ? sqrt(d) : 0.0;
-    }
-}
-
-// x = G^-1 rhs on the kept set (G^-1 = L^-T L^-1: L y = rhs, L^T x = y), 0 for a dropped monomial
-__host__ __device__ inline void wf_gram_solve(WfChol& f, const double (&rhs)[6], double (&x)[6]) {
-    double* y = f.y;
-    for (int a = 0; a < 6; ++a) {
-        x[a] = 0.0;
-        if (!f.kept[a]) continue;
-        double s = rhs[a];
-        for (int c = 0; c < a; ++c)
-            if (f.kept[c]) s -= f.L[a][c] * y[c];
-        y[a] = s / f.L[a][a];
-    }
-    for (int a = 5; a >= 0; --a) {
-        if (!f.kept[a]) continue;
-        double s = y[a];
-        for (int c = a + 1; c < 6; ++c)
-            if (f.kept[c]) s -= f.L[c][a] * x[c];
-        x[a] = s / f.L[a][a];
-    }
-}
-
-// normalised coordinates of the fit: u = (j - cx) / max(cx, 1), v likewise
-static void wf_fit_coords(int ny, int nx, WfFit& f) {
-    f.cx = 0.5 * (nx - 1);
-    f.cy = 0.5 * (ny - 1);
-    f.ixh = 1.0 / (nx > 1 ? f.cx : 1.0);
-    f.iyh = 1.0 / (ny > 1 ? f.cy : 1.0);
-}
-
-// Inverse Gram matrix of the six monomials on the (ny, nx) grid, float64.  The sums separate: sum u^a v^b = (sum_j u^a)(sum_i v^b).
-// A monomial that the grid cannot tell from the ones before it (a side of 1 or 2 nodes) is left out: its coefficient is 0.
-static void wf_gram_inverse(int ny, int nx, WfFit& f) {
-    wf_fit_coords(ny, nx, f);
-    double su[5] = {0, 0, 0, 0, 0}, sv[5] = {0, 0, 0, 0, 0};
-    for (int j = 0; j < nx; ++j) {
-        const double u = (j - f.cx) * f.ixh;
-        double p = 1.0;
-        for (int a = 0; a < 5; ++a, p *= u) su[a] += p;
-    }
-    for (int i = 0; i < ny; ++i) {
-        const double v = (i - f.cy) * f.iyh;
-        double p = 1.0;
-        for (int a = 0; a < 5; ++a, p *= v) sv[a] += p;
-    }
-    static const int pu[6] = {0, 1, 0, 2, 1, 0}, pv[6] = {0, 0, 1, 0, 1, 2};
-    double G[6][6];
-    for (int a = 0; a < 6; ++a)
-        for (int b = 0; b < 6; ++b) G[a][b] = su[pu[a] + pu[b]] * sv[pv[a] + pv[b]];
-    WfChol ch;
-    wf_gram_factor(G, ch);
-    for (int k = 0; k < 36; ++k) f.ginv[k] = 0.0;
-    for (int b = 0; b < 6; ++b) {     // column b of the inverse: the solve of the unit vector e_b
-        if (!ch.kept[b]) continue;
-        double rhs[6] = {}, x[6];
-        rhs[b] = 1.0;
-        wf_gram_solve(ch, rhs, x);
-        for (int a = 0; a < 6; ++a) f.ginv[6 * a + b] = x[a];
-    }
-}
-
 // ---- weighted / masked integration: preconditioned conjugate gradients on the weighted normal equations
 // A phi = b, started from 0, the unweighted DCT solve above as preconditioner.  Vectors are float32; every dot product is
 // accumulated in float64 per workgroup, written to the workspace and summed in index order by whoever needs it; alpha, beta and
@@ -400,13 +220,11 @@ static int wf_pcg_blocks(long long plane) {
     return (int)(b < WF_PCG_MAXBLOCKS ? b : WF_PCG_MAXBLOCKS);
 }
 
-static size_t wf_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // carves the caller's workspace; returns the bytes used (base == nullptr: size only)
 static size_t wf_pcg_layout(char* base, int n, int ny, int nx, WfPcg& g) {
-    const size_t plane = (size_t)ny * nx, fv = wf_align256((size_t)n * plane * sizeof(float));
+    const size_t plane = (size_t)ny * nx, fv = align256((size_t)n * plane * sizeof(float));
     const int nb = wf_pcg_blocks((long long)plane);
-    const size_t dv = wf_align256((size_t)n * nb * sizeof(double)), sv = wf_align256((size_t)n * sizeof(double));
+    const size_t dv = align256((size_t)n * nb * sizeof(double)), sv = align256((size_t)n * sizeof(double));
     size_t o = 0;
     float** fp[7] = {&g.weff, &g.cy, &g.cx, &g.r, &g.p, &g.qz, &g.t};
     for (auto f : fp) {
@@ -419,9 +237,9 @@ static size_t wf_pcg_layout(char* base, int n, int ny, int nx, WfPcg& g) {
         *d = (double*)(base + o);
         o += dv;
     }
-    g.state = (WfPcgState*)(base + o), o += wf_align256(2 * (size_t)n * sizeof(WfPcgState));
-    g.badpq = (int*)(base + o), o += wf_align256((size_t)n * sizeof(int));
-    g.flags = (int*)(base + o), o += wf_align256((size_t)n * sizeof(int));
+    g.state = (WfPcgState*)(base + o), o += align256(2 * (size_t)n * sizeof(WfPcgState));
+    g.badpq = (int*)(base + o), o += align256((size_t)n * sizeof(int));
+    g.flags = (int*)(base + o), o += align256((size_t)n * sizeof(int));
     g.n = n, g.ny = ny, g.nx = nx, g.nb = nb;
     return o;
 }
@@ -604,112 +422,6 @@ __global__ void __launch_bounds__(WF_PCG_THREADS) k_wf_wfinish(WfPcg g, int slot
     const size_t fo = (size_t)map * plane;
     for (int e = blockIdx.x * WF_PCG_THREADS + threadIdx.x; e < plane; e += g.nb * WF_PCG_THREADS)
         if (!(g.weff[fo + e] > 0.f)) x[fo + e] = __builtin_nanf("");
-}
-
-// ---- weighted fit: the 15 weighted monomial moments sum w u^a v^b (a + b <= 4) and the six weighted right-hand moments of a map
-// in float64, one workgroup per map; lane 0 forms the Gram matrix and solves it with the factorisation and drop rule of the unweighted fit.
-// A node counts only if its weight is finite and positive, so a NaN in the map at a weight-0 node is never read into a sum.
-constexpr int WF_WFIT_THREADS = 1024;
-__host__ __device__ constexpr int wf_midx(int a, int b) { return 5 * a - a * (a - 1) / 2 + b; }   // (a, b), a + b <= 4 -> 0 .. 14
-
-__device__ __forceinline__ float wf_fit_weight(const float* __restrict__ w, int e) {
-    const float a = w[e];
-    return (a > 0.f && isfinite(a)) ? a : 0.f;
-}
-
-__global__ void __launch_bounds__(WF_WFIT_THREADS) k_wf_poly2_wmoments(const float* __restrict__ phi, const float* __restrict__ w,
-                                                                      long long w_stride, int ny, int nx, WfFit f,
-                                                                      double* __restrict__ coeff) {
-    __shared__ double sh[WF_WFIT_THREADS / 64][21];
-    __shared__ struct {
-        double G[6][6], rhs[6], c[6];
-        WfChol ch;
-    } fit;
-    const int npix = ny * nx;
-    const float* __restrict__ p = phi + (size_t)blockIdx.x * npix;
-    const float* __restrict__ mw = w + (long long)blockIdx.x * w_stride;
-    double s[21];
-#pragma unroll
-    for (int k = 0; k < 21; ++k) s[k] = 0.0;
-    for (int e = threadIdx.x; e < npix; e += WF_WFIT_THREADS) {
-        const float wf = wf_fit_weight(mw, e);
-        if (!(wf > 0.f)) continue;
-        const int i = e / nx, j = e % nx;
-        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh, wd = (double)wf, x = wd * (double)p[e];
-        double up[5], vp[5];
-        up[0] = vp[0] = 1.0;
-#pragma unroll
-        for (int a = 1; a < 5; ++a) up[a] = up[a - 1] * u, vp[a] = vp[a - 1] * v;
-#pragma unroll
-        for (int a = 0; a < 5; ++a)
-#pragma unroll
-            for (int b = 0; a + b < 5; ++b) s[wf_midx(a, b)] += wd * up[a] * vp[b];
-        s[15] += x;
-        s[16] += u * x;
-        s[17] += v * x;
-        s[18] += u * u * x;
-        s[19] += u * v * x;
-        s[20] += v * v * x;
-    }
-    {   // lane k adds column k of the wave sums (thread 0 would hold 21 x 16 loads at once), thread 0 collects them
-        const double t = block_sum_columns(s, &sh[0][0], WF_WFIT_THREADS / 64);
-        if (threadIdx.x < 21) sh[0][threadIdx.x] = t;
-        __syncthreads();
-        if (threadIdx.x == 0)
-#pragma unroll
-            for (int k = 0; k < 21; ++k) s[k] = sh[0][k];
-    }
-    if (threadIdx.x == 0) {
-        constexpr int pu[6] = {0, 1, 0, 2, 1, 0}, pv[6] = {0, 0, 1, 0, 1, 2};
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            fit.rhs[a] = s[15 + a];
-#pragma unroll
-            for (int b = 0; b < 6; ++b) fit.G[a][b] = s[wf_midx(pu[a] + pu[b], pv[a] + pv[b])];
-        }
-        wf_gram_factor(fit.G, fit.ch);
-        wf_gram_solve(fit.ch, fit.rhs, fit.c);
-        for (int a = 0; a < 6; ++a) coeff[6 * (size_t)blockIdx.x + a] = fit.c[a];
-    }
-}
-
-// residual as k_wf_poly2_residual; rms = weighted population standard deviation sqrt(sum w r^2 / sum w - (sum w r / sum w)^2) over
-// the nodes of positive weight (NaN if there is none); weight-0 nodes get NaN when nan_invalid, else the same subtraction
-__global__ void __launch_bounds__(WF_FIT_THREADS) k_wf_poly2_wresidual(const float* phi, const float* __restrict__ w, long long w_stride,
-                                                                       int ny, int nx, WfFit f, const double* __restrict__ coeff,
-                                                                       unsigned mask, double scale, int nan_invalid, float* residual,
-                                                                       double* __restrict__ rms) {
-    __shared__ double sh[WF_FIT_THREADS / 64][3];
-    const int npix = ny * nx;
-    const float* p = phi + (size_t)blockIdx.x * npix;
-    const float* __restrict__ mw = w + (long long)blockIdx.x * w_stride;
-    float* q = residual + (size_t)blockIdx.x * npix;
-    double c[6];
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c[k] = ((mask >> k) & 1u) ? coeff[6 * (size_t)blockIdx.x + k] : 0.0;
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int e = threadIdx.x; e < npix; e += WF_FIT_THREADS) {
-        const float wf = wf_fit_weight(mw, e);
-        if (!(wf > 0.f) && nan_invalid) {
-            q[e] = __builtin_nanf("");
-            continue;
-        }
-        const int i = e / nx, j = e % nx;
-        const double u = ((double)j - f.cx) * f.ixh, v = ((double)i - f.cy) * f.iyh;
-        const double fit = c[0] + u * (c[1] + c[3] * u + c[4] * v) + v * (c[2] + c[5] * v);
-        const float out = (float)(scale * ((double)p[e] - fit));
-        q[e] = out;
-        if (wf > 0.f) {
-            s[0] += (double)wf;
-            s[1] += (double)wf * (double)out;
-            s[2] += (double)wf * (double)out * (double)out;
-        }
-    }
-    block_sum(s, &sh[0][0], WF_FIT_THREADS / 64);
-    if (threadIdx.x == 0) {
-        const double mean = s[0] > 0.0 ? s[1] / s[0] : 0.0;
-        rms[blockIdx.x] = s[0] > 0.0 ? sqrt(fmax(0.0, s[2] / s[0] - mean * mean)) : __builtin_nan("");
-    }
 }
 
 // z = M rhs: the four products of the DCT Poisson solve; `out` may be `rhs` itself, `scratch` is distinct from both; maps with a
@@ -907,7 +619,7 @@ using namespace b4d;
 
 extern "C" size_t b4d_phase_unwrap_workspace_bytes(int n, int ny, int nx) {
     if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
-    return 2 * wf_align256((size_t)n * ny * nx * sizeof(float));
+    return 2 * align256((size_t)n * ny * nx * sizeof(float));
 }
 
 extern "C" int b4d_phase_unwrap(const float* phase, int n, int ny, int nx, void* workspace, float* out, void* stream) {
@@ -916,7 +628,7 @@ extern "C" int b4d_phase_unwrap(const float* phase, int n, int ny, int nx, void*
     hipStream_t st = (hipStream_t)stream;
     const long long plane = (long long)ny * nx;
     float* p = (float*)workspace;
-    float* scratch = (float*)((char*)workspace + wf_align256((size_t)n * plane * sizeof(float)));
+    float* scratch = (float*)((char*)workspace + align256((size_t)n * plane * sizeof(float)));
     std::lock_guard<std::mutex> lk(wf_mutex());     // basis pointers stay valid until the launches below are queued
     const WfBasis *by = nullptr, *bx = nullptr;
     if (const int rc = wf_basis(ny, ny, &by)) return rc;
@@ -954,24 +666,6 @@ extern "C" int b4d_integrate_gradient(const float* gy, const float* gx, int n, i
     return B4D_OK;
 }
 
-extern "C" int b4d_poly2_fit(const float* w, int n, int ny, int nx, unsigned remove_mask, double scale, double* coeff, float* residual,
-                             double* rms, void* stream) {
-    if (!w || !coeff) return fail(B4D_EINVAL, "null argument");
-    if ((residual == nullptr) != (rms == nullptr)) return fail(B4D_EINVAL, "residual and rms go together (both or neither)");
-    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
-    if (remove_mask > 63u) return fail(B4D_EINVAL, "remove_mask has six bits");
-    if (!std::isfinite(scale)) return fail(B4D_EINVAL, "scale must be finite");
-    hipStream_t st = (hipStream_t)stream;
-    WfFit f;
-    wf_gram_inverse(ny, nx, f);
-    hipLaunchKernelGGL(k_wf_poly2_moments, dim3(n), dim3(WF_FIT_THREADS), 0, st, w, ny, nx, f, coeff);
-    if (residual)
-        hipLaunchKernelGGL(k_wf_poly2_residual, dim3(n), dim3(WF_FIT_THREADS), 0, st, w, ny, nx, f, (const double*)coeff, remove_mask,
-                           scale, residual, rms);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-
 extern "C" size_t b4d_integrate_weighted_workspace_bytes(int n, int ny, int nx) {
     if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
     WfPcg g;
@@ -1005,7 +699,7 @@ extern "C" int b4d_integrate_gradient_weighted(const float* gy, const float* gx,
 extern "C" size_t b4d_phase_unwrap_weighted_workspace_bytes(int n, int ny, int nx) {
     if (n < 1 || n > 65535 || ny < 1 || nx < 1 || ny > WF_MAX_SIDE || nx > WF_MAX_SIDE) return 0;
     WfPcg g;
-    return wf_pcg_layout(nullptr, n, ny, nx, g) + 2 * wf_align256((size_t)n * sizeof(int));
+    return wf_pcg_layout(nullptr, n, ny, nx, g) + 2 * align256((size_t)n * sizeof(int));
 }
 
 extern "C" int b4d_phase_unwrap_weighted(const float* phase, const float* w, long long w_stride, int n, int ny, int nx, double rtol,
@@ -1022,7 +716,7 @@ extern "C" int b4d_phase_unwrap_weighted(const float* phase, const float* w, lon
     WfPcg g;
     char* tail = (char*)workspace + wf_pcg_layout((char*)workspace, n, ny, nx, g);
     int* seed = (int*)tail;
-    float* shift = (float*)(tail + wf_align256((size_t)n * sizeof(int)));
+    float* shift = (float*)(tail + align256((size_t)n * sizeof(int)));
     g.tol2 = rtol * rtol;
     std::lock_guard<std::mutex> lk(wf_mutex());     // basis pointers stay valid until the launches below are queued
     const WfBasis *by = nullptr, *bx = nullptr;
@@ -1033,28 +727,6 @@ extern "C" int b4d_phase_unwrap_weighted(const float* phase, const float* w, lon
     if (const int rc = wf_pcg_solve(g, by, bx, 1.0, 1.0, max_iter, 0, out, iterations, residual, st)) return rc;
     hipLaunchKernelGGL(k_wf_unwrap_seed, dim3(n), block, 0, st, phase, g, (const float*)out, seed, shift);
     hipLaunchKernelGGL(k_wf_unwrap_wcongruence, grid, block, 0, st, phase, g, (const int*)seed, (const float*)shift, nan_invalid, out);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
-}
-
-extern "C" int b4d_poly2_fit_weighted(const float* w_map, const float* weights, long long weight_stride, int n, int ny, int nx,
-                                      unsigned remove_mask, double scale, int nan_invalid, double* coeff, float* residual, double* rms,
-                                      void* stream) {
-    if (!w_map || !weights || !coeff) return fail(B4D_EINVAL, "null argument");
-    if ((residual == nullptr) != (rms == nullptr)) return fail(B4D_EINVAL, "residual and rms go together (both or neither)");
-    if (const int rc = wf_check_grid(n, ny, nx)) return rc;
-    if (weight_stride != 0 && weight_stride != (long long)ny * nx)
-        return fail(B4D_EINVAL, "weight_stride is 0 (shared weights) or ny * nx (per map)");
-    if (remove_mask > 63u) return fail(B4D_EINVAL, "remove_mask has six bits");
-    if (!std::isfinite(scale)) return fail(B4D_EINVAL, "scale must be finite");
-    hipStream_t st = (hipStream_t)stream;
-    WfFit f;
-    wf_fit_coords(ny, nx, f);
-    for (double& v : f.ginv) v = 0.0;
-    hipLaunchKernelGGL(k_wf_poly2_wmoments, dim3(n), dim3(WF_WFIT_THREADS), 0, st, w_map, weights, weight_stride, ny, nx, f, coeff);
-    if (residual)
-        hipLaunchKernelGGL(k_wf_poly2_wresidual, dim3(n), dim3(WF_FIT_THREADS), 0, st, w_map, weights, weight_stride, ny, nx, f,
-                           (const double*)coeff, remove_mask, scale, nan_invalid, residual, rms);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
 }

@@ -8,7 +8,7 @@
 //               Xc[t][q] = x[t][p] - c[r][t] (float32), regions one after the other, each padded with zeros to whole chunks
 //               of TT_KC pixels; s[r][t] = float64 sum of the stored values.
 //   3. product  split-K SYRK on v_mfma_f32_32x32x2_f32: one workgroup per (chunk, frame-block pair bi <= bj inside the band),
-//               128 x 128 tile, four waves in 2 x 2 of 64 x 64 (the tiling of k_gram_mfma, b4d_eig.hip), K staged 32 deep
+//               128 x 128 tile, four waves in 2 x 2 of 64 x 64 (lane maps: b4d_mfma.hpp), K staged 32 deep
 //               through LDS with the next stage prefetched into registers; the accumulators are added into a second set and
 //               cleared every TT_RUN products (short fma chains).  The partial tile goes to the workspace: no communication
 //               between workgroups, no atomics.
@@ -26,6 +26,7 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
+#include "b4d_mfma.hpp"
 #include "b4d_reduce.hpp"
 
 namespace b4d {
@@ -36,8 +37,6 @@ constexpr int TT_TILE = 128;      // frame block
 constexpr int TT_U = 8;           // frames per step of the scan and pack loops
 constexpr int TT_MAX_T = 2048;
 constexpr int TT_MAX_R = 64;
-
-typedef float tt_f32x16 __attribute__((ext_vector_type(16)));
 
 struct TTMeta {
     long long N[TT_MAX_R];        // pixels of region r + 1
@@ -300,8 +299,7 @@ __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc
     int bi, bj;
     tt_pair(pair, nb, W, bi, bj);
     const bool diag = bi == bj;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wr = wave >> 1, wc = wave & 1, li = lane & 31, lk = lane >> 5;
+    const WaveTile t = wave_tile(threadIdx.x);
     const int m0 = bi * TT_TILE, n0 = bj * TT_TILE;
     // thread -> (row, 4 consecutive k) of the 128 x 32 stage, four rows 32 apart
     const int srow = threadIdx.x >> 3, sk = (threadIdx.x & 7) * 4;
@@ -315,13 +313,9 @@ __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc
         if (ia < T) ra[q] = *reinterpret_cast<const float4*>(col + (size_t)ia * (size_t)ktot + (k0));                       \
         if (!diag && ib < T) rb[q] = *reinterpret_cast<const float4*>(col + (size_t)ib * (size_t)ktot + (k0));              \
     }
-    tt_f32x16 acc[2][2], tot[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[a][b][r] = tot[a][b][r] = 0.f;
+    f32x16 acc[2][2], tot[2][2];
+    zero(acc);
+    zero(tot);
     const float* Bp = diag ? &As[0][0] : &Bs[0][0];
     TT_FETCH(0)
     for (int k0 = 0; k0 < TT_KC; k0 += 32) {
@@ -343,10 +337,11 @@ __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc
         if (k0 + 32 < TT_KC) {
             TT_FETCH(k0 + 32)
         }
+        // mma_slab of b4d_mfma.hpp written out: B is read through the flat pointer that selects the A slab on diagonal pairs
 #pragma unroll
         for (int kk = 0; kk < 32; kk += 2) {
-            const float a0 = As[kk + lk][64 * wr + li], a1 = As[kk + lk][64 * wr + 32 + li];
-            const float b0 = Bp[(kk + lk) * 129 + 64 * wc + li], b1 = Bp[(kk + lk) * 129 + 64 * wc + 32 + li];
+            const float a0 = As[kk + t.lk][64 * t.wr + t.li], a1 = As[kk + t.lk][64 * t.wr + 32 + t.li];
+            const float b0 = Bp[(kk + t.lk) * 129 + 64 * t.wc + t.li], b1 = Bp[(kk + t.lk) * 129 + 64 * t.wc + 32 + t.li];
             acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
             acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
             acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
@@ -354,29 +349,12 @@ __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc
         }
         __syncthreads();
         if ((k0 + 32) % TT_RUN == 0) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        tot[a][b][r] += acc[a][b][r];
-                        acc[a][b][r] = 0.f;
-                    }
+            tot[0][0] += acc[0][0], tot[0][1] += acc[0][1], tot[1][0] += acc[1][0], tot[1][1] += acc[1][1];
+            zero(acc);
         }
     }
     float* out = part + ((size_t)chunk * npairs + pair) * (TT_TILE * TT_TILE);
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-            const int n = 64 * wc + 32 * b + li;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int mm = 64 * wr + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * lk;
-                out[mm * TT_TILE + n] = tot[a][b][r];
-            }
-        }
+    for_each(tot, t, 0, 0, [&](int row, int col, float v) { out[row * TT_TILE + col] = v; });
 #undef TT_FETCH
 }
 
