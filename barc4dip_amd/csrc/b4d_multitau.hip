@@ -29,17 +29,13 @@
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
 #include "b4d_reduce.hpp"
+#include "b4d_regions.hpp"
 
 namespace b4d {
 
 constexpr int MT_RUN = 8;         // frames per float32 run of a lane's sums
-constexpr int MT_MAX_R = 64;
+constexpr int MT_MAX_R = RG_MAX_R;
 constexpr int MT_MAX_LEVELS = 24;
-
-struct MTMeta {
-    long long N[MT_MAX_R];        // pixels of region r + 1
-    int wstart[MT_MAX_R + 1];     // first wave of region r + 1; [R] = waves in use
-};
 
 struct MTLayout {
     int W;                        // waves (upper bound): npix / 64 + R
@@ -52,8 +48,6 @@ struct MTLayout {
     size_t o_pix, o_lab, o_cnt, o_base, o_meta, o_ring, o_buf0, o_buf1, o_cols, o_red, bytes;
     int c_P, c_Q, c_S, c_head, c_tail;
 };
-
-static inline size_t mt_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static bool mt_layout(long long npix, int R, int m, int L, int max_push, MTLayout& y) {
     if (npix < 1 || npix >= (1ll << 31) || R < 1 || R > MT_MAX_R || (m != 8 && m != 16 && m != 32) || L < 1 || L > MT_MAX_LEVELS ||
@@ -75,14 +69,14 @@ static bool mt_layout(long long npix, int R, int m, int L, int max_push, MTLayou
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
-        o += mt_up(bytes);
+        o += align256(bytes);
         return at;
     };
     y.o_pix = take(sizeof(int) * (size_t)y.Q);
     y.o_lab = take((size_t)npix);
     y.o_cnt = take(sizeof(int) * (size_t)y.nspan * R);
     y.o_base = take(sizeof(int) * (size_t)y.nspan * R);
-    y.o_meta = take(sizeof(MTMeta));
+    y.o_meta = take(sizeof(RegionMeta));
     y.o_ring = take(sizeof(float) * (size_t)L * m * (size_t)y.Q);
     y.o_buf0 = take(L > 1 ? sizeof(float) * (size_t)y.cap0 * (size_t)y.Q : 0);
     y.o_buf1 = take(L > 2 ? sizeof(float) * (size_t)y.cap1 * (size_t)y.Q : 0);
@@ -109,90 +103,22 @@ __global__ void __launch_bounds__(256) k_mt_scan(const float* __restrict__ x, in
     if (!fin) bad[p] = 1;
 }
 
-// ---- init a: effective labels as bytes (0 outside 1 .. R and where some frame is not finite) and pixels per (span, region).
+// ---- init, after region_list: pixel p of region r lands at lane 64 start[r] + (pixels of r before p).  pix was filled with -1.
 // grid (nspan), one wave
-__global__ void __launch_bounds__(64) k_mt_count(const int* __restrict__ labels, const uint8_t* __restrict__ bad, long long npix, int R,
-                                                 long long span, uint8_t* __restrict__ lab, int* __restrict__ cnt) {
-    __shared__ int n[MT_MAX_R + 1];
-    const int lane = threadIdx.x;
-    for (int r = lane; r <= MT_MAX_R; r += 64) n[r] = 0;
-    __syncthreads();
-    const long long p0 = (long long)blockIdx.x * span, p1 = min(npix, p0 + span);
-    for (long long g = p0; g < p1; g += 64) {
-        const long long p = g + lane;
-        int l = 0;
-        if (p < p1) {
-            l = labels ? labels[p] : 1;
-            if (l < 1 || l > R || (bad && bad[p])) l = 0;
-            lab[p] = (uint8_t)l;
-        }
-        unsigned long long todo = __ballot(l > 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int r = __shfl(l, lead, 64);
-            const unsigned long long mm = __ballot(l == r);
-            todo &= ~mm;
-            if (lane == lead) n[r] += __popcll(mm);
-        }
-    }
-    __syncthreads();
-    for (int r = lane; r < R; r += 64) cnt[(size_t)blockIdx.x * R + r] = n[r + 1];
-}
-
-// ---- init b: exclusive prefix of the counts over the spans, per region.  grid (R), one wave
-__global__ void __launch_bounds__(64) k_mt_prefix(const int* __restrict__ cnt, int nspan, int R, int* __restrict__ base,
-                                                  MTMeta* __restrict__ meta) {
-    __shared__ long long tot[64];
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const int per = (nspan + 63) / 64;
-    const int b0 = min(nspan, lane * per), b1 = min(nspan, b0 + per);
-    long long a = 0;
-    for (int b = b0; b < b1; ++b) a += cnt[(size_t)b * R + r];
-    tot[lane] = a;
-    __syncthreads();
-    long long run = 0;
-    for (int k = 0; k < lane; ++k) run += tot[k];
-    for (int b = b0; b < b1; ++b) {
-        base[(size_t)b * R + r] = (int)run;
-        run += cnt[(size_t)b * R + r];
-    }
-    if (lane == 63) meta->N[r] = run;
-}
-
-// ---- init c: wave ranges of the regions.  one thread
-__global__ void k_mt_segments(MTMeta* __restrict__ meta, int R) {
-    int w = 0;
-    for (int r = 0; r < R; ++r) {
-        meta->wstart[r] = w;
-        w += (int)((meta->N[r] + 63) / 64);
-    }
-    meta->wstart[R] = w;
-}
-
-// ---- init d: pixel p of region r lands at lane 64 wstart[r] + (pixels of r before p).  pix was filled with -1.  grid (nspan)
 __global__ void __launch_bounds__(64) k_mt_fill(const uint8_t* __restrict__ lab, long long npix, int R, long long span,
-                                                const int* __restrict__ base, const MTMeta* __restrict__ meta, int* __restrict__ pix) {
-    __shared__ int run[MT_MAX_R + 1];
+                                                const int* __restrict__ base, const RegionMeta* __restrict__ meta,
+                                                int* __restrict__ pix) {
+    __shared__ int run[RG_MAX_R + 1];
     const int lane = threadIdx.x;
     for (int r = lane; r < R; r += 64) run[r + 1] = base[(size_t)blockIdx.x * R + r];
     __syncthreads();
     const long long p0 = (long long)blockIdx.x * span, p1 = min(npix, p0 + span);
     for (long long g = p0; g < p1; g += 64) {
         const long long p = g + lane;
-        const int l = p < p1 ? (int)lab[p] : 0;
-        unsigned long long todo = __ballot(l > 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int r = __shfl(l, lead, 64);
-            const bool mine = l == r;
-            const unsigned long long mm = __ballot(mine);
-            todo &= ~mm;
-            const int rank = __popcll(mm & ((1ull << lane) - 1ull));
-            if (mine) pix[64ll * meta->wstart[r - 1] + run[r] + rank] = (int)p;
-            __syncthreads();    // every lane has read run[r]
-            if (lane == lead) run[r] += __popcll(mm);
-            __syncthreads();
-        }
+        for_each_label(p < p1 ? (int)lab[p] : 0, [&](int r, int lead, bool mine, unsigned long long mask) {
+            const long long dst = region_slot<64>(meta, run, r, lead, lane, mask);
+            if (mine) pix[dst] = (int)p;
+        });
     }
 }
 
@@ -203,12 +129,12 @@ __global__ void __launch_bounds__(64) k_mt_fill(const uint8_t* __restrict__ lab,
 // S: one column; head: M columns (the sums of the level's frames 0 .. M - 2).
 template <int M, int J0>
 __global__ void __launch_bounds__(64) k_mt_push(const float* __restrict__ src, long long stride, const int* __restrict__ pix, int c,
-                                                int n, long long Q, int W, int R, const MTMeta* __restrict__ meta,
+                                                int n, long long Q, int W, int R, const RegionMeta* __restrict__ meta,
                                                 float* __restrict__ ring, float* __restrict__ out, int cap, double* __restrict__ P,
                                                 double* __restrict__ Qs, double* __restrict__ S, double* __restrict__ head) {
     constexpr int NL = M - J0;
     const int w = blockIdx.x, lane = threadIdx.x;
-    if (w >= meta->wstart[R]) return;
+    if (w >= meta->start[R]) return;
     const long long q = 64ll * w + lane;
     const long long off = pix ? (long long)pix[q] : q;
     const bool live = off >= 0;
@@ -279,9 +205,9 @@ __global__ void __launch_bounds__(64) k_mt_push(const float* __restrict__ src, l
 // ---- finish a: tail[(l m + i) W + w] = the wave's sum of the i-th last frame of level l (0 where the level has fewer).
 // grid (W, L), one wave
 __global__ void __launch_bounds__(64) k_mt_tail(const float* __restrict__ ring, int T, int m, long long Q, int W, int R,
-                                                const MTMeta* __restrict__ meta, double* __restrict__ tail) {
+                                                const RegionMeta* __restrict__ meta, double* __restrict__ tail) {
     const int w = blockIdx.x, l = blockIdx.y, lane = threadIdx.x;
-    if (w >= meta->wstart[R]) return;
+    if (w >= meta->start[R]) return;
     const int Tl = T >> l;
     const float* rl = ring + (size_t)l * m * (size_t)Q + (size_t)(64ll * w + lane);
     for (int i = 0; i < m - 1; ++i) {
@@ -293,25 +219,20 @@ __global__ void __launch_bounds__(64) k_mt_tail(const float* __restrict__ ring, 
 
 // ---- finish b: red[col R + r] = sum of column col over the region's waves: thread t adds the waves t, t + 256, ... of the region in
 // order, then a fixed tree.  grid (ncols, R), block 256
-__global__ void __launch_bounds__(256) k_mt_colsum(const double* __restrict__ cols, int W, int R, const MTMeta* __restrict__ meta,
+__global__ void __launch_bounds__(256) k_mt_colsum(const double* __restrict__ cols, int W, int R, const RegionMeta* __restrict__ meta,
                                                    double* __restrict__ red) {
     __shared__ double sh[256];
     const int col = blockIdx.x, r = blockIdx.y;
-    const int w0 = meta->wstart[r], w1 = meta->wstart[r + 1];
+    const int w0 = meta->start[r], w1 = meta->start[r + 1];
     double a = 0.0;
     for (int w = w0 + threadIdx.x; w < w1; w += 256) a += cols[(size_t)col * W + w];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) red[(size_t)col * R + r] = sh[0];
+    a = block_tree_sum256(a, sh, false);
+    if (threadIdx.x == 0) red[(size_t)col * R + r] = a;
 }
 
 // ---- finish c: one thread per (region, lag).  grid ceil(R n_lags / 64)
 __global__ void __launch_bounds__(64) k_mt_final(const double* __restrict__ red, int T, int m, int L, int R, int n_lags, int NS,
-                                                 const MTMeta* __restrict__ meta, double* __restrict__ g2, double* __restrict__ g2_err,
+                                                 const RegionMeta* __restrict__ meta, double* __restrict__ g2, double* __restrict__ g2_err,
                                                  double* __restrict__ mean, long long* __restrict__ n_pixels) {
     const int id = blockIdx.x * 64 + threadIdx.x;
     if (id >= R * n_lags) return;
@@ -356,7 +277,7 @@ __global__ void __launch_bounds__(64) k_mt_final(const double* __restrict__ red,
 
 template <int M>
 static void mt_launch_level(bool first, int W, hipStream_t st, const float* src, long long stride, const int* pix, int c, int n,
-                            long long Q, int R, const MTMeta* meta, float* ring, float* out, int cap, double* P, double* Qs, double* S,
+                            long long Q, int R, const RegionMeta* meta, float* ring, float* out, int cap, double* P, double* Qs, double* S,
                             double* head) {
     if (first)
         hipLaunchKernelGGL((k_mt_push<M, 0>), dim3(W), dim3(64), 0, st, src, stride, pix, c, n, Q, W, R, meta, ring, out, cap, P, Qs, S,
@@ -427,13 +348,11 @@ extern "C" int b4d_multi_tau_init(const int* labels, const unsigned char* bad, l
     int* pix = reinterpret_cast<int*>(w + y.o_pix);
     int* cnt = reinterpret_cast<int*>(w + y.o_cnt);
     int* base = reinterpret_cast<int*>(w + y.o_base);
-    MTMeta* meta = reinterpret_cast<MTMeta*>(w + y.o_meta);
+    RegionMeta* meta = reinterpret_cast<RegionMeta*>(w + y.o_meta);
     B4D_HIP(hipMemsetAsync(pix, 0xFF, sizeof(int) * (size_t)y.Q, st));
     B4D_HIP(hipMemsetAsync(w + y.o_ring, 0, sizeof(float) * (size_t)n_levels * m * (size_t)y.Q, st));
     B4D_HIP(hipMemsetAsync(w + y.o_cols, 0, sizeof(double) * (size_t)y.ncols * y.W, st));
-    hipLaunchKernelGGL(k_mt_count, dim3(y.nspan), dim3(64), 0, st, labels, bad, npix, R, y.span, lab, cnt);
-    hipLaunchKernelGGL(k_mt_prefix, dim3(R), dim3(64), 0, st, cnt, y.nspan, R, base, meta);
-    hipLaunchKernelGGL(k_mt_segments, dim3(1), dim3(1), 0, st, meta, R);
+    region_list(labels, false, bad, npix, R, y.span, y.nspan, 64, lab, cnt, base, meta, nullptr, st);
     hipLaunchKernelGGL(k_mt_fill, dim3(y.nspan), dim3(64), 0, st, lab, npix, R, y.span, base, meta, pix);
     B4D_HIP(hipGetLastError());
     return B4D_OK;
@@ -449,7 +368,7 @@ extern "C" int b4d_multi_tau_push(const float* frames, long long t0, int n, long
     hipStream_t st = (hipStream_t)stream;
     char* w = static_cast<char*>(workspace);
     const int* pix = reinterpret_cast<const int*>(w + y.o_pix);
-    const MTMeta* meta = reinterpret_cast<const MTMeta*>(w + y.o_meta);
+    const RegionMeta* meta = reinterpret_cast<const RegionMeta*>(w + y.o_meta);
     float* ring = reinterpret_cast<float*>(w + y.o_ring);
     float* buf[2] = {reinterpret_cast<float*>(w + y.o_buf0), reinterpret_cast<float*>(w + y.o_buf1)};
     double* cols = reinterpret_cast<double*>(w + y.o_cols);
@@ -495,7 +414,7 @@ extern "C" int b4d_multi_tau_finish(long long T, long long npix, int n_regions, 
     if (n_lags < 0) return n_lags;
     hipStream_t st = (hipStream_t)stream;
     char* w = static_cast<char*>(workspace);
-    const MTMeta* meta = reinterpret_cast<const MTMeta*>(w + y.o_meta);
+    const RegionMeta* meta = reinterpret_cast<const RegionMeta*>(w + y.o_meta);
     const float* ring = reinterpret_cast<const float*>(w + y.o_ring);
     double* cols = reinterpret_cast<double*>(w + y.o_cols);
     double* red = reinterpret_cast<double*>(w + y.o_red);

@@ -141,6 +141,21 @@ __device__ __forceinline__ void block_sum_all(double (&v)[NV], double* sh, int n
     }
 }
 
+// Halving tree over a workgroup of exactly 256 threads, which must all call; sh: 256 doubles of LDS.  Thread t brings its partial a:
+// sh[t] = a, then sh[t] += sh[t + o] for o = 128, 64, .., 1 with a barrier per step; every thread returns sh[0].  again: the caller
+// writes sh again (a second call) before its next barrier, so a trailing barrier is passed.
+__device__ __forceinline__ double block_tree_sum256(double a, double* sh, bool again) {
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double t = sh[0];
+    if (again) __syncthreads();
+    return t;
+}
+
 // Workgroup arg-max by argmax_merge's rule: every lane brings its own (bv, bi) and every lane returns with the merged pair of the
 // workgroup: wave_argmax, then every lane merges the waves 1 .. nwaves - 1 into wave 0's pair in order.  sv / si: LDS, one word
 // per wave (nwaves = blockDim.x / 64).  It contains a barrier: the WHOLE workgroup must call it, and sv / si must not be written

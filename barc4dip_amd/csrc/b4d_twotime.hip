@@ -4,7 +4,7 @@
 // rank-k update over the region's pixels.  The stages, all on the caller's stream:
 //   1. scan     one wave per (pixel span, frame slice): float64 sums and counts of the finite pixels per (span, region, frame),
 //               and a flag per labelled pixel that is non-finite in some frame.  Offsets c[r][t] = float32(provisional mean).
-//   2. pack     effective labels, pixel counts per (span, region), prefix -> every pixel's place in its region's raster order;
+//   2. pack     the region list (b4d_regions.hpp) with a chunk as granule -> every pixel's place in its region's raster order;
 //               Xc[t][q] = x[t][p] - c[r][t] (float32), regions one after the other, each padded with zeros to whole chunks
 //               of TT_KC pixels; s[r][t] = float64 sum of the stored values.
 //   3. product  split-K SYRK on v_mfma_f32_32x32x2_f32: one workgroup per (chunk, frame-block pair bi <= bj inside the band),
@@ -28,6 +28,7 @@
 #include "b4d_common.hpp"
 #include "b4d_mfma.hpp"
 #include "b4d_reduce.hpp"
+#include "b4d_regions.hpp"
 
 namespace b4d {
 
@@ -36,12 +37,7 @@ constexpr int TT_RUN = 256;       // products per float32 fma chain: the chunk's
 constexpr int TT_TILE = 128;      // frame block
 constexpr int TT_U = 8;           // frames per step of the scan and pack loops
 constexpr int TT_MAX_T = 2048;
-constexpr int TT_MAX_R = 64;
-
-struct TTMeta {
-    long long N[TT_MAX_R];        // pixels of region r + 1
-    int cstart[TT_MAX_R + 1];     // first chunk of region r + 1; [R] = chunks in use
-};
+constexpr int TT_MAX_R = RG_MAX_R;
 
 struct TTLayout {
     int nb, W, npairs;            // frame blocks, largest block distance inside the band, block pairs
@@ -50,8 +46,6 @@ struct TTLayout {
     long long nchunks, ktot;      // upper bound of the chunks in use; row length of Xc
     size_t o_xc, o_part, o_psum, o_pcnt, o_lab, o_bad, o_cnt, o_base, o_c, o_s, o_meta, bytes;
 };
-
-static inline size_t tt_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 static bool tt_layout(int T, long long npix, int R, int L, TTLayout& y) {
     if (T < 2 || T > TT_MAX_T || npix < 1 || npix >= (1ll << 31) || R < 1 || R > TT_MAX_R || L < 0 || L > T - 1) return false;
@@ -69,7 +63,7 @@ static bool tt_layout(int T, long long npix, int R, int L, TTLayout& y) {
     size_t o = 0;
     auto take = [&](size_t bytes) {
         const size_t at = o;
-        o += tt_up(bytes);
+        o += align256(bytes);
         return at;
     };
     y.o_xc = take(sizeof(float) * (size_t)T * (size_t)y.ktot);
@@ -82,7 +76,7 @@ static bool tt_layout(int T, long long npix, int R, int L, TTLayout& y) {
     y.o_base = take(sizeof(int) * (size_t)y.nscan * R);
     y.o_c = take(sizeof(float) * (size_t)R * T);
     y.o_s = take(sizeof(double) * (size_t)R * T);
-    y.o_meta = take(sizeof(TTMeta));
+    y.o_meta = take(sizeof(RegionMeta));
     y.bytes = o;
     return true;
 }
@@ -91,12 +85,7 @@ static bool tt_layout(int T, long long npix, int R, int L, TTLayout& y) {
 __global__ void __launch_bounds__(256) k_tt_labels(const int* __restrict__ labels, long long npix, int R, uint8_t* __restrict__ lab) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= npix) return;
-    int v = 1;
-    if (labels) {
-        v = labels[p];
-        if (v < 1 || v > R) v = 0;
-    }
-    lab[p] = (uint8_t)v;
+    lab[p] = (uint8_t)region_label(labels, p, R);
 }
 
 // ---- 1. scan: grid (nscan, tz), one wave.  psum / pcnt[(span * R + r) * T + t] += sum / count over the span's pixels of label
@@ -111,11 +100,7 @@ __global__ void __launch_bounds__(64) k_tt_scan(const float* __restrict__ x, int
         const long long p = g + lane;
         const int l = p < p1 ? (int)lab[p] : 0;
         bool allfin = true;
-        unsigned long long todo = __ballot(l > 0);
-        while (todo) {
-            const int r = __shfl(l, __ffsll((long long)todo) - 1, 64);
-            const bool mine = l == r;
-            todo &= ~__ballot(mine);
+        for_each_label(l, [&](int r, int, bool mine, unsigned long long) {
             for (int t = t0; t < t1; t += TT_U) {
                 float v[TT_U];
 #pragma unroll
@@ -139,7 +124,7 @@ __global__ void __launch_bounds__(64) k_tt_scan(const float* __restrict__ x, int
                     pcnt[at] += mc;
                 }
             }
-        }
+        });
         if (l > 0 && !allfin) bad[p] = 1;
     }
 }
@@ -165,72 +150,13 @@ __global__ void __launch_bounds__(64) k_tt_colsum(const double* __restrict__ psu
     }
 }
 
-// ---- 2a. effective labels (0 where some frame is non-finite) and pixels per (span, region).  grid (nscan), one wave
-__global__ void __launch_bounds__(64) k_tt_count(uint8_t* __restrict__ lab, const uint8_t* __restrict__ bad, long long npix, int R,
-                                                 long long span, int* __restrict__ cnt) {
-    __shared__ int n[TT_MAX_R + 1];
-    const int lane = threadIdx.x;
-    for (int r = lane; r <= TT_MAX_R; r += 64) n[r] = 0;
-    __syncthreads();
-    const long long p0 = (long long)blockIdx.x * span, p1 = min(npix, p0 + span);
-    for (long long g = p0; g < p1; g += 64) {
-        const long long p = g + lane;
-        int l = 0;
-        if (p < p1) {
-            l = bad[p] ? 0 : (int)lab[p];
-            lab[p] = (uint8_t)l;
-        }
-        unsigned long long todo = __ballot(l > 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int r = __shfl(l, lead, 64);
-            const unsigned long long m = __ballot(l == r);
-            todo &= ~m;
-            if (lane == lead) n[r] += __popcll(m);
-        }
-    }
-    __syncthreads();
-    for (int r = lane; r < R; r += 64) cnt[(size_t)blockIdx.x * R + r] = n[r + 1];
-}
-
-// ---- 2b. exclusive prefix of the counts over the spans, per region: lane l takes the spans [l * per, (l + 1) * per).
-// grid (R), one wave
-__global__ void __launch_bounds__(64) k_tt_prefix(const int* __restrict__ cnt, int nscan, int R, int* __restrict__ base,
-                                                  TTMeta* __restrict__ meta) {
-    __shared__ long long tot[64];
-    const int r = blockIdx.x, lane = threadIdx.x;
-    const int per = (nscan + 63) / 64;
-    const int b0 = min(nscan, lane * per), b1 = min(nscan, b0 + per);
-    long long a = 0;
-    for (int b = b0; b < b1; ++b) a += cnt[(size_t)b * R + r];
-    tot[lane] = a;
-    __syncthreads();
-    long long run = 0;
-    for (int k = 0; k < lane; ++k) run += tot[k];
-    for (int b = b0; b < b1; ++b) {
-        base[(size_t)b * R + r] = (int)run;
-        run += cnt[(size_t)b * R + r];
-    }
-    if (lane == 63) meta->N[r] = run;
-}
-
-// ---- 2c. chunk ranges of the regions and the pixel counts handed to the caller.  one thread
-__global__ void k_tt_segments(TTMeta* __restrict__ meta, int R, long long* __restrict__ n_pixels) {
-    int c = 0;
-    for (int r = 0; r < R; ++r) {
-        meta->cstart[r] = c;
-        c += (int)((meta->N[r] + TT_KC - 1) / TT_KC);
-        n_pixels[r] = meta->N[r];
-    }
-    meta->cstart[R] = c;
-}
-
-// ---- 2d. pack: grid (nscan, tz), one wave.  Pixel p of region r lands at column cstart[r] * TT_KC + (pixels of r before p).
+// ---- 2. pack, after region_list: grid (nscan, tz), one wave.  Pixel p of region r lands at column start[r] * TT_KC + (pixels of r
+// before p).
 __global__ void __launch_bounds__(64) k_tt_pack(const float* __restrict__ x, int T, long long npix, int R, long long span, int fz,
                                                 const uint8_t* __restrict__ lab, const int* __restrict__ base,
-                                                const TTMeta* __restrict__ meta, const float* __restrict__ c, float* __restrict__ Xc,
+                                                const RegionMeta* __restrict__ meta, const float* __restrict__ c, float* __restrict__ Xc,
                                                 long long ktot, double* __restrict__ psum) {
-    __shared__ int run[TT_MAX_R + 1];
+    __shared__ int run[RG_MAX_R + 1];
     const int lane = threadIdx.x;
     for (int r = lane; r < R; r += 64) run[r + 1] = base[(size_t)blockIdx.x * R + r];
     __syncthreads();
@@ -239,15 +165,8 @@ __global__ void __launch_bounds__(64) k_tt_pack(const float* __restrict__ x, int
     for (long long g = p0; g < p1; g += 64) {
         const long long p = g + lane;
         const int l = p < p1 ? (int)lab[p] : 0;
-        unsigned long long todo = __ballot(l > 0);
-        while (todo) {
-            const int lead = __ffsll((long long)todo) - 1;
-            const int r = __shfl(l, lead, 64);
-            const bool mine = l == r;
-            const unsigned long long m = __ballot(mine);
-            todo &= ~m;
-            const int rank = __popcll(m & ((1ull << lane) - 1ull));
-            const long long dst = (long long)meta->cstart[r - 1] * TT_KC + run[r] + rank;
+        for_each_label(l, [&](int r, int lead, bool mine, unsigned long long mask) {
+            const long long dst = region_slot<TT_KC>(meta, run, r, lead, lane, mask);
             for (int t = t0; t < t1; t += TT_U) {
                 double ms = 0.0;
 #pragma unroll
@@ -262,17 +181,14 @@ __global__ void __launch_bounds__(64) k_tt_pack(const float* __restrict__ x, int
                 }
                 if (lane < TT_U && t + lane < t1) psum[((size_t)blockIdx.x * R + (r - 1)) * T + t + lane] += ms;
             }
-            __syncthreads();    // every lane has read run[r]
-            if (lane == lead) run[r] += __popcll(m);
-            __syncthreads();
-        }
+        });
     }
 }
 
-// ---- 2e. zeros behind each region's last pixel, up to the end of its last chunk.  grid (R, T)
-__global__ void __launch_bounds__(256) k_tt_padzero(const TTMeta* __restrict__ meta, float* __restrict__ Xc, long long ktot) {
+// ---- 2b. zeros behind each region's last pixel, up to the end of its last chunk.  grid (R, T)
+__global__ void __launch_bounds__(256) k_tt_padzero(const RegionMeta* __restrict__ meta, float* __restrict__ Xc, long long ktot) {
     const int r = blockIdx.x;
-    const long long a = (long long)meta->cstart[r] * TT_KC + meta->N[r], b = (long long)meta->cstart[r + 1] * TT_KC;
+    const long long a = (long long)meta->start[r] * TT_KC + meta->N[r], b = (long long)meta->start[r + 1] * TT_KC;
     float* row = Xc + (size_t)blockIdx.y * (size_t)ktot;
     for (long long q = a + threadIdx.x; q < b; q += 256) row[q] = 0.f;
 }
@@ -291,11 +207,11 @@ __device__ __forceinline__ void tt_pair(int pair, int nb, int W, int& bi, int& b
 // ---- 3. product: grid (nchunks * npairs), pair fastest so that the pairs of a chunk run side by side; block 256 = 4 waves in 2 x 2,
 // each a 64 x 64 tile (4 accumulators of 16 registers).  part[(chunk * npairs + pair)][128][128] = A_bi A_bj^T over the chunk.
 __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc, long long ktot, int T, int R, int nb, int W, int npairs,
-                                                 const TTMeta* __restrict__ meta, float* __restrict__ part) {
+                                                 const RegionMeta* __restrict__ meta, float* __restrict__ part) {
     __shared__ float As[32][129];
     __shared__ float Bs[32][129];
     const int chunk = blockIdx.x / npairs, pair = blockIdx.x % npairs;
-    if (chunk >= meta->cstart[R]) return;
+    if (chunk >= meta->start[R]) return;
     int bi, bj;
     tt_pair(pair, nb, W, bi, bj);
     const bool diag = bi == bj;
@@ -360,7 +276,7 @@ __global__ void __launch_bounds__(256, 2) k_tt_syrk(const float* __restrict__ Xc
 
 // ---- 4a. covariances of the upper triangle inside the band, means and variances.  grid (64, npairs, R), block 256
 __global__ void __launch_bounds__(256) k_tt_reduce(const float* __restrict__ part, int T, int R, int nb, int W, int npairs, int L,
-                                                   const TTMeta* __restrict__ meta, const float* __restrict__ c,
+                                                   const RegionMeta* __restrict__ meta, const float* __restrict__ c,
                                                    const double* __restrict__ s, double* __restrict__ out, double* __restrict__ mean,
                                                    double* __restrict__ var) {
     const int elem = blockIdx.x * 256 + threadIdx.x, pair = blockIdx.y, r = blockIdx.z;
@@ -372,7 +288,7 @@ __global__ void __launch_bounds__(256) k_tt_reduce(const float* __restrict__ par
     double cov = NAN, m = NAN;
     if (N > 0) {
         double G = 0.0;
-        for (int ch = meta->cstart[r]; ch < meta->cstart[r + 1]; ++ch)
+        for (int ch = meta->start[r]; ch < meta->start[r + 1]; ++ch)
             G += (double)part[((size_t)ch * npairs + pair) * (TT_TILE * TT_TILE) + elem];
         const double n = (double)N, si = s[(size_t)r * T + i] / n, sj = s[(size_t)r * T + j] / n;
         cov = G / n - si * sj;
@@ -415,26 +331,15 @@ __global__ void __launch_bounds__(256) k_tt_lags(const double* __restrict__ M, i
     __shared__ double sh[256];
     const int tau = blockIdx.x, r = blockIdx.y, n = T - tau;
     const double* D = M + (size_t)r * T * T + tau;
-    auto total = [&](double a) {
-        sh[threadIdx.x] = a;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-            __syncthreads();
-        }
-        const double t = sh[0];
-        __syncthreads();
-        return t;
-    };
     double a = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) a += D[(size_t)i * (T + 1)];
-    const double mu = total(a) / n;
+    const double mu = block_tree_sum256(a, sh, true) / n;
     double q = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) {
         const double d = D[(size_t)i * (T + 1)] - mu;
         q = fma(d, d, q);
     }
-    const double ss = total(q);
+    const double ss = block_tree_sum256(q, sh, false);
     if (threadIdx.x == 0) {
         g2[(size_t)r * (L + 1) + tau] = mu;
         g2_err[(size_t)r * (L + 1) + tau] = sqrt(ss / n) / sqrt((double)n);
@@ -477,7 +382,7 @@ static int tt_run(const float* stack, int T, long long npix, const int* labels, 
     int* base = reinterpret_cast<int*>(w + y.o_base);
     float* c = reinterpret_cast<float*>(w + y.o_c);
     double* s = reinterpret_cast<double*>(w + y.o_s);
-    TTMeta* meta = reinterpret_cast<TTMeta*>(w + y.o_meta);
+    RegionMeta* meta = reinterpret_cast<RegionMeta*>(w + y.o_meta);
     const size_t pbytes = sizeof(double) * (size_t)y.nscan * R * T;
 
     if (ev) B4D_HIP(hipEventRecord(ev[0], st));
@@ -488,9 +393,7 @@ static int tt_run(const float* stack, int T, long long npix, const int* labels, 
     hipLaunchKernelGGL(k_tt_scan, dim3(y.nscan, y.tz), dim3(64), 0, st, stack, T, npix, R, y.span, y.fz, lab, bad, psum, pcnt);
     hipLaunchKernelGGL(k_tt_colsum, dim3(R * T), dim3(64), 0, st, psum, pcnt, y.nscan, R, T, c, s);
     if (ev) B4D_HIP(hipEventRecord(ev[1], st));
-    hipLaunchKernelGGL(k_tt_count, dim3(y.nscan), dim3(64), 0, st, lab, bad, npix, R, y.span, cnt);
-    hipLaunchKernelGGL(k_tt_prefix, dim3(R), dim3(64), 0, st, cnt, y.nscan, R, base, meta);
-    hipLaunchKernelGGL(k_tt_segments, dim3(1), dim3(1), 0, st, meta, R, n_pixels);
+    region_list(nullptr, true, bad, npix, R, y.span, y.nscan, TT_KC, lab, cnt, base, meta, n_pixels, st);
     B4D_HIP(hipMemsetAsync(psum, 0, pbytes, st));
     hipLaunchKernelGGL(k_tt_pack, dim3(y.nscan, y.tz), dim3(64), 0, st, stack, T, npix, R, y.span, y.fz, lab, base, meta, c, Xc, y.ktot,
                        psum);

@@ -14,10 +14,9 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
-from .twotime import _host
+from ._regions import MAX_REGIONS, region_map, stack_shape
 
 LAGS_PER_LEVEL = (8, 16, 32)
-MAX_REGIONS = 64
 MAX_LEVELS = 24
 
 
@@ -54,45 +53,17 @@ def _check(images, labels, mask, lags_per_level, max_level, chunk_frames):
         if not streamed:
             images = np.asarray(images)
         shape, kind = tuple(int(s) for s in images.shape), np.dtype(images.dtype).kind
-    if kind == "c":
-        raise NotImplementedError("complex input is not supported by the HIP path (real frames only).")
-    if len(shape) != 3 or 0 in shape:
-        raise ValueError(f"images must be a non-empty (T, H, W) stack, got shape {tuple(shape)}")
-    T, H, W = shape
-    if T < 2:
-        raise ValueError("multi_tau_correlation needs at least two frames")
+    T, H, W = stack_shape(shape, kind == "c", "multi_tau_correlation")
     if isinstance(lags_per_level, bool) or lags_per_level not in LAGS_PER_LEVEL:
         raise ValueError(f"lags_per_level must be one of {LAGS_PER_LEVEL}, got {lags_per_level!r}")
     if max_level is not None and (isinstance(max_level, bool) or int(max_level) != max_level or int(max_level) < 0):
         raise ValueError(f"max_level must be an integer >= 0 or None, got {max_level!r}")
     if isinstance(chunk_frames, bool) or int(chunk_frames) != chunk_frames or int(chunk_frames) < 1:
         raise ValueError(f"chunk_frames must be an integer >= 1, got {chunk_frames!r}")
-    if labels is not None and mask is not None:
-        raise ValueError("pass labels or mask, not both")
-    lab, R = None, 1
-    if labels is not None:
-        lab = _host(labels)
-        if lab.shape != (H, W):
-            raise ValueError(f"labels must have the frame shape {(H, W)}, got {lab.shape}")
-        if lab.dtype.kind not in "iu":
-            raise ValueError(f"labels must be an integer map, got dtype {lab.dtype}")
-        if lab.min() < 0:
-            raise ValueError("labels must not be negative (0 = not used, 1 .. R = regions)")
-        R = int(lab.max())
-        if R < 1:
-            raise ValueError("labels names no region (all zero)")
-    elif mask is not None:
-        mk = _host(mask)
-        if mk.shape != (H, W):
-            raise ValueError(f"mask must have the frame shape {(H, W)}, got {mk.shape}")
-        if mk.dtype.kind not in "biu":
-            raise ValueError(f"mask must be a bool map, got dtype {mk.dtype}")
-        lab = mk.astype(bool)
+    lab, R = region_map(labels, mask, H, W)
     if R > MAX_REGIONS or H * W >= 2 ** 31 or T >= 2 ** 31:
         raise NotImplementedError(f"multi_tau_correlation: at most {MAX_REGIONS} regions, fewer than 2^31 pixels per frame and fewer "
                                   f"than 2^31 frames (got T = {T}, R = {R}, {H} x {W})")
-    if lab is not None:
-        lab = np.ascontiguousarray(lab, dtype=np.int32)
     return images, streamed, kind, T, H, W, lab, R, int(lags_per_level), (None if max_level is None else int(max_level))
 
 

@@ -13,15 +13,11 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from ._regions import MAX_REGIONS, _host, region_map, stack_shape
 
 NORMS = {"pearson": 0, "intensity": 1, "covariance": 2}
 MAX_FRAMES = 2048
-MAX_REGIONS = 64
 CHUNK = 2048            # pixels of a region per float32 accumulation (TT_KC, csrc/b4d_twotime.hip)
-
-
-def _host(a) -> np.ndarray:
-    return a.detach().cpu().numpy() if D.is_tensor(a) else np.asarray(a)
 
 
 def _check(images, labels, mask, norm, max_lag):
@@ -31,13 +27,7 @@ def _check(images, labels, mask, norm, max_lag):
     else:
         images = np.asarray(images)
         shape, cplx = images.shape, np.iscomplexobj(images)
-    if cplx:
-        raise NotImplementedError("complex input is not supported by the HIP path (real frames only).")
-    if len(shape) != 3 or 0 in shape:
-        raise ValueError(f"images must be a non-empty (T, H, W) stack, got shape {tuple(shape)}")
-    T, H, W = shape
-    if T < 2:
-        raise ValueError("two_time_correlation needs at least two frames")
+    T, H, W = stack_shape(shape, cplx, "two_time_correlation")
     if norm not in NORMS:
         raise ValueError(f"norm must be one of {sorted(NORMS)}, got {norm!r}")
     if max_lag is None:
@@ -46,32 +36,10 @@ def _check(images, labels, mask, norm, max_lag):
         if isinstance(max_lag, bool) or int(max_lag) != max_lag or not 0 <= int(max_lag) <= T - 1:
             raise ValueError(f"max_lag must be an integer in 0 .. T - 1 = {T - 1}, got {max_lag!r}")
         L = int(max_lag)
-    if labels is not None and mask is not None:
-        raise ValueError("pass labels or mask, not both")
-    lab, R = None, 1
-    if labels is not None:
-        lab = _host(labels)
-        if lab.shape != (H, W):
-            raise ValueError(f"labels must have the frame shape {(H, W)}, got {lab.shape}")
-        if lab.dtype.kind not in "iu":
-            raise ValueError(f"labels must be an integer map, got dtype {lab.dtype}")
-        if lab.min() < 0:
-            raise ValueError("labels must not be negative (0 = not used, 1 .. R = regions)")
-        R = int(lab.max())
-        if R < 1:
-            raise ValueError("labels names no region (all zero)")
-    elif mask is not None:
-        m = _host(mask)
-        if m.shape != (H, W):
-            raise ValueError(f"mask must have the frame shape {(H, W)}, got {m.shape}")
-        if m.dtype.kind not in "biu":
-            raise ValueError(f"mask must be a bool map, got dtype {m.dtype}")
-        lab = m.astype(bool)
+    lab, R = region_map(labels, mask, H, W)
     if T > MAX_FRAMES or R > MAX_REGIONS or H * W >= 2 ** 31:
         raise NotImplementedError(f"two_time_correlation: T <= {MAX_FRAMES}, at most {MAX_REGIONS} regions and fewer than 2^31 "
                                   f"pixels per frame (got T = {T}, R = {R}, {H} x {W})")
-    if lab is not None:
-        lab = np.ascontiguousarray(lab, dtype=np.int32)
     return T, H, W, lab, R, NORMS[norm], L
 
 
