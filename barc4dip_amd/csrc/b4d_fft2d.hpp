@@ -411,8 +411,9 @@ __device__ __forceinline__ void store_cols(float2* __restrict__ rowp, const floa
 // (a workgroup barrier that leaves them in flight) ahead of the eight of set 1, so set 0 is complete after half of the tile and goes
 // through stage 1 ... exchange 2 while set 1 lands (Fft3::run_sets_staged).  For that no twiddle may queue behind set 1's loads: every
 // lane loads one entry of the 1024-point table and one of the 64 stage-2 values first of all and puts them into LDS behind the
-// exchange region before that barrier.  The tile is written back in the plain [row][column] form (every lane has read all of it by
-// then), so the inverse row pass and k_nyq do not change.  Bit-identical to CS = 0.
+// exchange region before that barrier; the tables stay there, and the inverse transform reads its twiddles from them as well.  The
+// direct PSD stores (whole lines) are non-temporal.  The tile is written back in the plain [row][column] form (every lane has read
+// all of it by then), so the inverse row pass and k_nyq do not change.  Bit-identical to CS = 0.
 template <int NY, int MODE, int UNIT = 0, int YS = 0, int CS = 0>
 __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WAVES_PER_EU)) k_col(ColArgs p) {
     using Cfg = ColCfg<NY, YS>;
@@ -547,9 +548,15 @@ __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WA
             for (int k = 0; k < NC; ++k) pw[k] = v[k][j].x * v[k][j].x + v[k][j].y * v[k][j].y;
             if (psd) {
                 const unsigned rd = (unsigned)((ky + NYF / 2) & (NYF - 1)) * nx, rm = (unsigned)((NYF / 2 - ky) & (NYF - 1)) * nx;
-                *at_bytes<f32x2>(psd, (rd + nx / 2 + kx0) * 4u) = f32x2{pw[0] * s, pw[1] * s};
+                // direct half.  Column sets: 16 lanes write one whole aligned 128-byte line that nobody else touches -- streamed past
+                // L2 (-2 % on the kernel); the 16-column tiles' half lines meet their other half there and stay cached
+                if constexpr (CS != 0)
+                    __builtin_nontemporal_store(f32x2{pw[0] * s, pw[1] * s}, at_bytes<f32x2>(psd, (rd + nx / 2 + kx0) * 4u));
+                else
+                    *at_bytes<f32x2>(psd, (rd + nx / 2 + kx0) * 4u) = f32x2{pw[0] * s, pw[1] * s};
                 // Hermitian mirror: columns nx/2 - kx0 - 1, nx/2 - kx0 (column 0 has no mirror).  Two dword stores: ONE 8-byte
-                // store on the 4-byte boundary (the mirror of an aligned pair starts one float off) measured +6 % on the kernel
+                // store on the 4-byte boundary (the mirror of an aligned pair starts one float off) measured +6 % on the kernel.
+                // Cached on every route: the dwords merge into sectors in L2
                 const unsigned mo = (rm + nx / 2 - kx0 - 1) * 4u;
                 *at_bytes<float>(psd, mo) = pw[1] * s;
                 if (kx0 >= 1) *at_bytes<float>(psd, mo + 4u) = pw[0] * s;
@@ -573,7 +580,15 @@ __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WA
     const int cp2 = tid2 % CPT, u2 = tid2 / CPT;
     const unsigned toff2 = (unsigned)u2 * CT + NC * cp2;
     __syncthreads();
-    Fft3<G, 1>::template run_sets<NC / 2>(w, u2, cp2, lds, tw2);
+    if constexpr (CS != 0) {
+        // the two tables are still in LDS behind the exchange region: no twiddle of the inverse queues behind the 48 PSD stores
+        // (30 global loads per lane less; the same products, -3 % on the kernel)
+        Fft3<G, 1>::template run_sets_staged<NC / 2>(w, u2, cp2, lds, lds + (size_t)G::LDS_ELEMS * CPT,
+                                                     lds + (size_t)G::LDS_ELEMS * CPT + G::M);
+        Fft3<G, 1>::stage3(w[0]);
+    } else {
+        Fft3<G, 1>::template run_sets<NC / 2>(w, u2, cp2, lds, tw2);
+    }
     B4D_STAMP(5);
     // V[y] = Ga[y] + i Gb[y] with Ga, Gb Hermitian in y: split with V[-y], one set at a time through the exchange region
     float2 vr[NC / 2][E];
@@ -596,8 +611,8 @@ __global__ void __launch_bounds__((ColCfg<NY, YS>::THREADS), (ColCfg<NY, YS>::WA
             c[2 * h + 1] = make_float2(0.5f * (z.y + zr.y), 0.5f * (zr.x - z.x));
         }
         // streaming (non-temporal) stores: the tile is read once more, by the row pass, after a gigabyte of other traffic -- kept
-        // out of L2 it leaves the cache to the PSD half lines that do meet there (-3 % on this kernel; the PSD stores themselves
-        // must stay cached: non-temporal they doubled the kernel)
+        // out of L2 it leaves the cache to the PSD half lines that do meet there (-3 % on this kernel; PSD stores that are half
+        // lines or single dwords must stay cached: non-temporal they doubled the kernel)
         // rows the row pass reads: pairs (2q, 2q + 1) up to 2q = NY/2; YS: rows 0 .. NY/2 of both parity tiles
         if (!p.half_rows || u2 + T * j <= (YS ? NY / 2 : NY / 2 + 1)) {
             __builtin_nontemporal_store(f32x4{c[0].x, c[0].y, c[1].x, c[1].y},
