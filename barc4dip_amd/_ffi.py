@@ -119,6 +119,7 @@ SIGNATURES = {
     "b4d_stepping_fit": (_i, [_vp, _i, _i, C.c_longlong, _i, _vp, _vp, _vp, _d, _vp, _vp, _vp, _vp]),
     "b4d_stepping_compare": (_i, [_vp, _vp, C.c_longlong, _i, _i, C.c_longlong, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "b4d_stepping_calibrate_step": (_i, [_vp, _i, C.c_longlong, _vp, _vp, _vp, _d, _vp, _vp]),
+    "b4d_speckle_scan": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

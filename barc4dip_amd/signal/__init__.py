@@ -1,12 +1,13 @@
 """GPU drop-in for ``barc4dip.signal`` (same public names as signal/__init__.py:6-26)."""
 from __future__ import annotations
 
-from . import corr, displacement, fft, focus, fringes, modal, speckle, stepping, tracking, wavefront
+from . import corr, displacement, fft, focus, fringes, modal, scanning, speckle, stepping, tracking, wavefront
 from .corr import autocorr2d, autocorr2d_stack, psd_autocorr2d_stack, xcorr2d
 from .displacement import displacement_grid, displacement_map
 from .focus import beam_caustic, focal_spot, focus_geometry
 from .fringes import (coarse_carriers, fringe_carriers, fringe_demodulate, fringe_displacement, fringe_grid, phase_unwrap)
 from .modal import modal_eval, modal_fit, modal_table
+from .scanning import speckle_scan
 from .speckle import speckle_contrast, speckle_imaging
 from .stepping import calibrate_steps, phase_stepping, stepping_displacement, stepping_fit
 from .tracking import (phase_correlation, phase_correlation_batch, template_matching, template_matching_batch,
@@ -26,4 +27,5 @@ __all__ = [
     "fringes", "fringe_grid", "fringe_demodulate", "phase_unwrap", "coarse_carriers", "fringe_carriers", "fringe_displacement",
     "speckle", "speckle_contrast", "speckle_imaging",
     "stepping", "stepping_fit", "phase_stepping", "calibrate_steps", "stepping_displacement",
+    "scanning", "speckle_scan",
 ]

@@ -706,6 +706,34 @@ int b4d_stepping_compare(const float* sample, const float* reference, long long 
 int b4d_stepping_calibrate_step(const float* stack, int T, long long npix, const double* basis, const double* gram_inv,
                                 const double* delta, double saturation, double* out, void* stream);
 
+/* Speckle scanning (speckle-vector tracking, "UMPA") at detector resolution (barc4dip_amd.signal.speckle_scan; DESIGN.md
+ * section 24).  ref (n, h, w) and samples (m, n, h, w): DEVICE float32, the same n diffuser positions without and with the
+ * sample, m scans against one reference; weights: DEVICE (n,) float64, g[n] >= 0 and not all 0 (the caller checks; a scan
+ * without a position of weight above 0 comes back NaN).  A position of weight 0 is never read.
+ * Taper per axis h_w[j] = 1 (taper 0) or 0.5 - 0.5 cos(2 pi (j + 0.5) / w) (taper 1); pooled weights
+ * W[n][j][i] = g[n] h_wy[j] h_wx[i] / (sum g sum h_wy sum h_wx).  For pixel p and the shift u = (uy, ux), |uy| <= search_y,
+ * |ux| <= search_x, the reference window is centred on p and the sample window on p + u (the convention of
+ * b4d_displacement_map); Rm, VR are the mean and variance of R[n][p + .] under W, Sm(u), VS(u) those of S[n][p + u + .] and
+ * C(u) the covariance of the two, all pooled over n and the window.  rho(u) = C(u) / sqrt(VR VS(u)); a candidate is undefined
+ * when VR <= 1e-12 Rm^2 or VS(u) <= 1e-12 Sm(u)^2.  The peak u* is the defined candidate of largest rho, the first in row-major
+ * order (uy, then ux ascending) among equals.  With subpixel = 1 each axis adds d = 0.5 (a - c) / (a - 2 b + c) clipped to
+ * +-0.5 from a, b, c = rho(u* - e), rho(u*), rho(u* + e); d = 0 when a - 2 b + c >= 0, when a neighbour is undefined or when
+ * u* lies on the border of the search range on that axis (which also sets the edge flag, with subpixel = 0 too).
+ * out: DEVICE (m, 6, h, w) float64, planar:
+ *   0 dy, 1 dx = u* + d     2 correlation = rho(u*)     3 transmission = Sm(u*) / Rm
+ *   4 dark_field = C(u*) / (VR transmission)            5 flags: 1.0 valid, + 2.0 edge
+ * A pixel is NaN in planes 0 .. 4 with flags 0 when its margin (win / 2 + search per axis) leaves the frame, when a reference
+ * value of its window or a sample value of its window grown by the search is not finite in a position of weight above 0, or
+ * when no candidate is defined; such a value counts as 0 for every other pixel, which keeps the bits it has with 0 in its place.
+ * All sums are float64, of values shifted by one pixel of the workgroup's tile; each product R_n[q] S_n[q + u] is formed once
+ * and shared by the windows that cover q through a separable filter.  Two launches on `stream`, no atomics, every sum in a fixed
+ * order: a scan gives the same bits alone and inside any batch.  Works in the library's per-stream scratch buffer
+ * (16 (1 + m) h w bytes).
+ * Limits: odd win <= 31, 0 <= search <= 16 per axis, n <= 4096 (B4D_ESIZE beyond); an even window, a frame smaller than
+ * win + 2 search, m > 65534 or h w >= 2^31: B4D_EINVAL.  All argument errors are returned before any launch.               */
+int b4d_speckle_scan(const float* ref, const float* samples, int m, int n, int h, int w, int win_y, int win_x, int search_y,
+                     int search_x, const double* weights, int taper, int subpixel, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
