@@ -8,8 +8,10 @@ from .statistics import distribution_moments
 from . import sharded
 from .temporal import temporal_stats
 from .multitau import multi_tau_correlation
+from . import order
+from .order import temporal_median, temporal_percentile, temporal_robust_mean
 from .twotime import correlation_decay, two_time_correlation
 
-__all__ = ["sharpness", "sharpness_stats", "sharpness_stack_stats", "statistics", "speckles", "speckle_stats",
+__all__ = ["order", "temporal_median", "temporal_percentile", "temporal_robust_mean","sharpness", "sharpness_stats", "sharpness_stack_stats", "statistics", "speckles", "speckle_stats",
            "speckle_stack_stats", "distribution_moments", "temporal", "temporal_stats", "sharded", "kernels", "twotime",
            "two_time_correlation", "correlation_decay", "multitau", "multi_tau_correlation"]

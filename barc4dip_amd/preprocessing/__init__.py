@@ -7,6 +7,7 @@ from .distortion import correct_distortion, remove_distortion
 from .filters import deconvolve_psf
 from .normalize import flat_field_correction
 from .rank import median_filter, percentile_filter, rank_filter, remove_outliers
+from .combine import combine_frames, remove_zingers
 
 __all__ = ["deconvolve_psf", "flat_field_correction", "distortion", "correct_distortion", "remove_distortion",
-           "median_filter", "rank_filter", "percentile_filter", "remove_outliers"]
+           "median_filter", "rank_filter", "percentile_filter", "remove_outliers", "combine_frames", "remove_zingers"]

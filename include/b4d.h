@@ -734,6 +734,43 @@ int b4d_stepping_calibrate_step(const float* stack, int T, long long npix, const
 int b4d_speckle_scan(const float* ref, const float* samples, int m, int n, int h, int w, int win_y, int win_x, int search_y,
                      int search_x, const double* weights, int taper, int subpixel, double* out, void* stream);
 
+/* Per-pixel order statistics along the frame axis of a stack (barc4dip_amd.metrics.order, barc4dip_amd.preprocessing.combine;
+ * DESIGN.md section 25).  stack: DEVICE (T, npix) float32, frames frame_stride >= npix elements apart; the caller offsets the base
+ * pointers to address a pixel range (the convention of b4d_temporal_accumulate_range).  Per pixel the samples are sorted in
+ * np.sort's order (NaN above +Inf, -0 below +0).
+ * b4d_temporal_quantiles: q HOST, n_q fractions in [0, 1], 1 <= n_q <= 8; out DEVICE (n_q, npix) float32; n_valid DEVICE (npix)
+ *   uint16, the non-NaN samples per pixel, or NULL.  nan_policy 0 "propagate": all T samples take part and a pixel with any NaN
+ *   is NaN in every output (np.percentile, np.median); 1 "omit": the n non-NaN samples take part, n = 0 gives NaN
+ *   (np.nanpercentile, np.nanmedian).  With s[0 .. n) the sorted samples taking part and h = q (n - 1) in float64, method
+ *     0 linear: i = floor(h), g = h - i      1 lower: i = floor(h), g = 0      2 higher: i = ceil(h), g = 0
+ *     3 nearest: i = rint(h), half to even, g = 0      4 midpoint: i = floor(h), g = 0.5 if h > i, else 0.
+ *   g == 0: the result is s[i] itself; otherwise (float) (a + (b - a) g), a = (double) s[i], b = (double) s[i + 1], the
+ *   difference, product and sum each rounded once in float64.  The median is q = 0.5 with the midpoint method.
+ * b4d_temporal_robust_mean: a sample that is not finite takes no part (it sorts as NaN and is always rejected); n is the count of
+ *   finite samples, med the midpoint median of them (NaN for n = 0), d_t = x_t - med in float32, mad the midpoint median of
+ *   |d_t|.  A sample is rejected, in float32 and in b4d_despeckle's operation order, when
+ *     scale_kind 0 "absolute": |d| > threshold
+ *     scale_kind 1 "mad"     : |d| > threshold * max(1.4826f * mad, min_scale)
+ *     scale_kind 2 "poisson" : d * d > (threshold * threshold) * max(med, min_scale), the square formed in float32 on the host
+ *   (max as np.maximum), restricted by polarity 0 both, 1 hot (and d > 0), 2 dead (and d < 0).  If more than half of a pixel's
+ *   samples are equal, mad is 0: with min_scale = 0 every differing sample is then rejected.
+ *   mean (npix) float32 = (float) (sum of the kept x_t / n_kept) in float64, NaN for n_kept = 0; the kept samples are added in
+ *   eight partial sums, partial s over t = s, s + 8, .. in ascending t, joined as ((P0 + P1) + (P2 + P3)) + ((P4 + P5) + (P6 + P7)).
+ *   Optional (NULL to skip): median (npix) float32; scale (npix) float32, the right-hand side of the test that was applied;
+ *   n_kept (npix) uint16; rejected (T, npix) bytes and cleaned (T, npix) float32 (a rejected sample replaced by med), both with
+ *   rows out_stride >= npix elements apart.
+ * Limits: 1 <= T <= 1024 (B4D_ESIZE above).  B4D_EINVAL: frame_stride or out_stride < npix, a q outside [0, 1] or not finite,
+ *   n_q, method, nan_policy, scale_kind, polarity or flags out of range, a negative (or NaN) threshold or min_scale, an output
+ *   that overlaps the stack.  All argument errors are returned before any launch.
+ * T <= 64 sorts the samples in registers (one read of the stack; wide accesses where npix, the strides and every base allow,
+ *   dword accesses otherwise); longer stacks, and any T with flags bit 0, select by counting on a tile in LDS.  Both routes and
+ *   all access widths give the same bits.  No atomics; asynchronous on `stream`, no host synchronisation.                     */
+int b4d_temporal_quantiles(const float* stack, int T, long long frame_stride, long long npix, const double* q, int n_q, int method,
+                           int nan_policy, int flags, float* out, unsigned short* n_valid, void* stream);
+int b4d_temporal_robust_mean(const float* stack, int T, long long frame_stride, long long npix, int scale_kind, float threshold,
+                             float min_scale, int polarity, int flags, float* mean, float* median, float* scale, unsigned short* n_kept,
+                             unsigned char* rejected, float* cleaned, long long out_stride, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
