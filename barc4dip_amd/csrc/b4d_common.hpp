@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdint>
 #include <mutex>
 #include <string>
 
@@ -18,6 +19,13 @@ inline int fail(int code, const std::string& msg) {
 }
 // workspace carving: sizes rounded up to 256 bytes
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+// pointer predicates of the entry points: p on a multiple of `bytes` (a power of two; null is aligned), and whether two byte
+// ranges share an address (a null pointer never overlaps)
+inline bool ptr_aligned(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+inline bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t bbytes) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
+}
 // lazily grown device scratch for second-stage reductions (b4d_stats.hip), one buffer per caller stream
 int get_scratch(size_t bytes, void** out, hipStream_t stream);
 // serialises the host side of every entry point that works in a scratch buffer (re-entrant calls from several host

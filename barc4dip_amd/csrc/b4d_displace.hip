@@ -234,7 +234,7 @@ __global__ void __launch_bounds__(DM_THREADS) k_displace(DispArgs a) {
     for (int k = tid; k < nm; k += nthr) M[k] = fabsf(M[k]);
     __syncthreads();
     unsigned nl, ne;
-    const float med = key2f(radix_select<1>(M, (unsigned)nm, (unsigned)nm / 2, reinterpret_cast<unsigned*>(B), sh, nl, ne));
+    const float med = keys::from_key(radix_select<1>(M, (unsigned)nm, (unsigned)nm / 2, reinterpret_cast<unsigned*>(B), sh, nl, ne));
     if (tid != 0) return;
     const size_t win = ((size_t)blockIdx.z * a.gy + blockIdx.y) * a.gx + blockIdx.x;
     auto c = [&](int di, int dj) { return nb9[(di + 1) * 3 + dj + 1]; };

@@ -1166,9 +1166,8 @@ struct Route {
     int colsets;           // parity route with row16, nx <= 2048: column-set tiles between the forward row pass and the column pass
                            // ("colsets"); BOTH launchers check the workspace's alignment (colsets_of)
 };
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // the one decision the forward row pass and the column pass must share: which layout the tiles between them have
-static inline int colsets_of(const Route& rt, const void* spec) { return rt.parity && rt.row16 && aligned16(spec) ? rt.colsets : 0; }
+static inline int colsets_of(const Route& rt, const void* spec) { return rt.parity && rt.row16 && ptr_aligned(spec, 16) ? rt.colsets : 0; }
 
 // Launchers: one per pass, the route (YS: parity tiles) a template argument.  A dispatcher instantiates every kernel it names in the
 // including unit: the plain-route ones (dispatch_r2c, dispatch_c2r) are ordinary functions, the *_route templates let the one unit
@@ -1226,7 +1225,7 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
     if constexpr (YS) {
         // 16-byte stores need a 16-byte-aligned workspace (the loads are dwords: the frames may sit anywhere); the narrow kernel otherwise
         if constexpr (SEQ % 2 == 0) {
-            if (colsets && row16 && aligned16(spec)) {   // couples of transforms: one group of SEQ pairs per workgroup
+            if (colsets && row16 && ptr_aligned(spec, 16)) {   // couples of transforms: one group of SEQ pairs per workgroup
                 if (ct_w != 32 || (pl->ny / 2) % SEQ) return fail(B4D_ESIZE, "column-set tiles: 32 columns, whole workgroups");
                 hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, 1, true, true, true>), grid, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny,
                                    ct_w, srcs, pl->tw_y);
@@ -1236,7 +1235,7 @@ static int launch_r2c(const b4d_plan* pl, const float* in, float2* spec, float* 
         } else if (colsets) {
             return fail(B4D_ESIZE, "column-set tiles need two transforms per workgroup");
         }
-        if (row16 && aligned16(spec))
+        if (row16 && ptr_aligned(spec, 16))
             hipLaunchKernelGGL((k_row_r2c<NX, SEQ, false, ITER, true, true>), grid_full, block, 0, st, in, spec, nyq_rows, pl->tw_x, pl->ny,
                                ct_w, srcs, pl->tw_y);
         else
@@ -1307,7 +1306,7 @@ static int launch_c2r(const b4d_plan* pl, const RowOutArgs& a, int batch, int mo
     }
     if constexpr (YS) {
         // 16-byte accesses need 16-byte-aligned output (the C ABI does not promise it) and workspace: the narrow kernel otherwise
-        if (row16 && aligned16(a.g) && aligned16(a.out))
+        if (row16 && ptr_aligned(a.g, 16) && ptr_aligned(a.out, 16))
             hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS, true>), grid, block, 0, st, a);
         else
             hipLaunchKernelGGL((k_row_c2r<NX, SEQ, C2R_OUT, B4D_UNIT_TAG, YS>), grid, block, 0, st, a);

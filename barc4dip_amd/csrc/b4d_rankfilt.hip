@@ -2,7 +2,7 @@
 // (batch, ny, nx) float32 frames, frame by frame), the range-only variant behind utils/range.py:14-86 of the reference, the fused
 // outlier repair and the uint16 scaling of utils/dtype.py:15-53.
 //
-// One workgroup per output tile.  The tile and its halo are staged ONCE in LDS as ordered integer keys (b4d_rankfilt.hpp): the
+// One workgroup per output tile.  The tile and its halo are staged ONCE in LDS as ordered integer keys (b4d_keys.hpp): the
 // border rule runs only while the halo of an edge tile is filled, NaN rules cost nothing afterwards, and every compare-exchange
 // is an integer min / max.  A rank filter is a selection, so on finite input the output is bit-identical to SciPy's.
 //   register route: median of 3 x 3 / 5 x 5 / 7 x 7; a lane produces four outputs adjacent in x from S rows of twelve keys
@@ -240,21 +240,11 @@ __global__ void __launch_bounds__(256) k_range_final(uint32_t* __restrict__ mm, 
     }
 }
 
-struct DespeckleArgs {
-    int scale_kind;    // 0 absolute, 1 mad, 2 poisson
-    float threshold;   // poisson: threshold * threshold, formed in float32 on the host
-    float min_scale;
-    int polarity;      // 0 both, 1 hot, 2 dead
-};
-
-// np.maximum(s, floor): NaN stays NaN
-__device__ __forceinline__ float max_keep_nan(float s, float floor_) { return s < floor_ ? floor_ : s; }
-
-// out = median where the centre pixel is an outlier, else the pixel: one read of the frame, one write.  Every float32 operation is
-// rounded on its own (no product feeds an add), in the order of the table in DESIGN.md, so a NumPy model reproduces the mask exactly.
+// out = median where the centre pixel is an outlier (the rule of b4d_keys.hpp against the window's median and, for the mad scale
+// only, the window's MAD), else the pixel: one read of the frame, one write.
 template <int S>
 __global__ void __launch_bounds__(256) k_despeckle(const float* __restrict__ in, int ny, int nx, int mode, float cval, float* __restrict__ out,
-                                                   unsigned char* __restrict__ mask, unsigned long long* __restrict__ counts, DespeckleArgs a,
+                                                   unsigned char* __restrict__ mask, unsigned long long* __restrict__ counts, OutlierRule a,
                                                    int vec_in, int vec_out, int vec_mask) {
     constexpr int R = S / 2;
     __shared__ __attribute__((aligned(16))) uint32_t lds[(RF_TY + 2 * R) * RF_LW];
@@ -280,24 +270,16 @@ __global__ void __launch_bounds__(256) k_despeckle(const float* __restrict__ in,
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
                 const float m = from_key(med[c]);
-                const float d = __fsub_rn(x[c], m);
-                bool o;
+                float mad = 0.f;
                 if (a.scale_kind == 1) {
                     uint32_t v[S * S];
 #pragma unroll
                     for (int j = 0; j < S; ++j)
 #pragma unroll
                         for (int i = 0; i < S; ++i) v[j * S + i] = to_key(fabsf(__fsub_rn(from_key(w[j][4 + c - R + i]), m)));
-                    const float mad = from_key(median_forgetful<KeyOps, S * S>(v));
-                    o = fabsf(d) > __fmul_rn(a.threshold, max_keep_nan(__fmul_rn(1.4826f, mad), a.min_scale));
-                } else if (a.scale_kind == 2) {
-                    o = __fmul_rn(d, d) > __fmul_rn(a.threshold, max_keep_nan(m, a.min_scale));
-                } else {
-                    o = fabsf(d) > a.threshold;
+                    mad = from_key(median_forgetful<KeyOps, S * S>(v));
                 }
-                if (a.polarity == 1) o = o && d > 0.f;
-                if (a.polarity == 2) o = o && d < 0.f;
-                if ((float_bits(x[c]) & 0x7F800000u) == 0x7F800000u) o = true;   // a non-finite centre pixel is always an outlier
+                const bool o = outlier_rejected(a, x[c], m, outlier_rhs(a, m, mad));
                 res[c] = o ? m : x[c];
                 flag[c] = o ? 1 : 0;
                 if (ox + c < nx) cnt += flag[c];
@@ -358,11 +340,6 @@ __global__ void __launch_bounds__(256) k_scale_u16_vec(const float* __restrict__
     }
 }
 
-static bool overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 constexpr int MAX_GRID_Z = 65535;
 
 template <int S>
@@ -373,7 +350,7 @@ static void launch_median_reg(const float* in, int frames, int ny, int nx, int m
 }
 template <int S>
 static void launch_despeckle(const float* in, int frames, int ny, int nx, int mode, float cval, float* out, unsigned char* mask,
-                             unsigned long long* counts, DespeckleArgs a, int vec_in, int vec_out, int vec_mask, hipStream_t st) {
+                             unsigned long long* counts, OutlierRule a, int vec_in, int vec_out, int vec_mask, hipStream_t st) {
     hipLaunchKernelGGL(k_despeckle<S>, dim3((nx + RF_TX - 1) / RF_TX, (ny + RF_TY - 1) / RF_TY, frames), dim3(256), 0, st, in, ny, nx, mode, cval,
                        out, mask, counts, a, vec_in, vec_out, vec_mask);
 }
@@ -390,12 +367,12 @@ extern "C" int b4d_rank_filter(const float* in, int batch, int ny, int nx, int s
     if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_rank_filter: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     if (!out && !minmax) return fail(B4D_EINVAL, "b4d_rank_filter: out and minmax are both null");
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
-    if (overlaps(in, bytes, out, bytes) || overlaps(in, bytes, minmax, 8 * (size_t)batch) || overlaps(out, bytes, minmax, 8 * (size_t)batch))
+    if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(in, bytes, minmax, 8 * (size_t)batch) || ranges_overlap(out, bytes, minmax, 8 * (size_t)batch))
         return fail(B4D_EINVAL, "b4d_rank_filter: in, out and minmax must not overlap");
     if ((ny + GN_TY - 1) / GN_TY > 65535) return fail(B4D_ESIZE, "b4d_rank_filter: more than 65535 row tiles");
     hipStream_t st = (hipStream_t)stream;
     uint32_t* mm = reinterpret_cast<uint32_t*>(minmax);
-    const int vec_in = (nx % 4 == 0 && aligned16(in)) ? 1 : 0, vec_out = (out && nx % 4 == 0 && aligned16(out)) ? 1 : 0;
+    const int vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0, vec_out = (out && nx % 4 == 0 && ptr_aligned(out, 16)) ? 1 : 0;
     const bool reg = !(flags & 1) && size_y == size_x && (size_y == 3 || size_y == 5 || size_y == 7) && rank == size_y * size_x / 2;
     if (mm) hipLaunchKernelGGL(k_range_init, dim3((batch + 255) / 256), dim3(256), 0, st, mm, batch);
     for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Z) {
@@ -423,18 +400,14 @@ extern "C" int b4d_despeckle(const float* in, int batch, int ny, int nx, int siz
     if (!(threshold >= 0.f) || !(min_scale >= 0.f)) return fail(B4D_EINVAL, "b4d_despeckle: threshold and min_scale must be >= 0");
     if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_despeckle: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     const size_t fpix = (size_t)ny * nx, npix = fpix * batch, bytes = npix * sizeof(float);
-    if (overlaps(in, bytes, out, bytes) || overlaps(in, bytes, mask, npix) || overlaps(out, bytes, mask, npix) ||
-        overlaps(in, bytes, counts, 8 * (size_t)batch) || overlaps(out, bytes, counts, 8 * (size_t)batch))
+    if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(in, bytes, mask, npix) || ranges_overlap(out, bytes, mask, npix) ||
+        ranges_overlap(in, bytes, counts, 8 * (size_t)batch) || ranges_overlap(out, bytes, counts, 8 * (size_t)batch))
         return fail(B4D_EINVAL, "b4d_despeckle: buffers must not overlap");
     if ((ny + RF_TY - 1) / RF_TY > 65535) return fail(B4D_ESIZE, "b4d_despeckle: more than 65535 row tiles");
     hipStream_t st = (hipStream_t)stream;
-    DespeckleArgs a;
-    a.scale_kind = scale_kind;
-    a.threshold = scale_kind == 2 ? threshold * threshold : threshold;
-    a.min_scale = min_scale;
-    a.polarity = polarity;
-    const int vec_in = (nx % 4 == 0 && aligned16(in)) ? 1 : 0, vec_out = (nx % 4 == 0 && aligned16(out)) ? 1 : 0;
-    const int vec_mask = (mask && nx % 4 == 0 && (reinterpret_cast<uintptr_t>(mask) & 3) == 0) ? 1 : 0;
+    const OutlierRule a = make_outlier_rule(scale_kind, threshold, min_scale, polarity);
+    const int vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0, vec_out = (nx % 4 == 0 && ptr_aligned(out, 16)) ? 1 : 0;
+    const int vec_mask = (mask && nx % 4 == 0 && ptr_aligned(mask, 4)) ? 1 : 0;
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
     if (cnt) B4D_HIP(hipMemsetAsync(cnt, 0, 8 * (size_t)batch, st));
     for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Z) {
@@ -453,10 +426,10 @@ extern "C" int b4d_despeckle(const float* in, int batch, int ny, int nx, int siz
 
 extern "C" int b4d_scale_to_u16(const float* in, size_t n, float vmin, double inv, int mul_f64, unsigned short* out, void* stream) {
     if (!in || !out || n < 1) return fail(B4D_EINVAL, "b4d_scale_to_u16: bad argument");
-    if (overlaps(in, n * sizeof(float), out, n * sizeof(unsigned short))) return fail(B4D_EINVAL, "b4d_scale_to_u16: in and out must not overlap");
+    if (ranges_overlap(in, n * sizeof(float), out, n * sizeof(unsigned short))) return fail(B4D_EINVAL, "b4d_scale_to_u16: in and out must not overlap");
     hipStream_t st = (hipStream_t)stream;
     size_t done = 0;
-    if (aligned16(in) && (reinterpret_cast<uintptr_t>(out) & 7) == 0 && n >= 4) {
+    if (ptr_aligned(in, 16) && ptr_aligned(out, 8) && n >= 4) {
         const size_t nvec = n / 4;
         hipLaunchKernelGGL(k_scale_u16_vec, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 65535)), dim3(256), 0, st, in, nvec, vmin, inv, mul_f64,
                            out);

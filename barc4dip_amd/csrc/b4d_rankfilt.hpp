@@ -1,63 +1,19 @@
-// b4d_rankfilt.hpp -- ordered integer keys and selection networks of the spatial rank filters (b4d_rankfilt.hip).
-// Everything here is __host__ __device__ and free of HIP types, so a plain C++ program can include it and test the networks
-// (tests/test_rank_filter_host.py).  A network is written against an operations policy O (O::T, O::lo, O::hi): the kernels run
-// it on 32-bit keys with integer min / max, the host test also on 64 zero-one patterns at a time (lo = AND, hi = OR).
+// b4d_rankfilt.hpp -- what is spatial in the rank filters (b4d_rankfilt.hip): the selection networks of the 3 x 3 .. 7 x 7 windows
+// and the border rule.  The keys, the operations policy O and cex come from b4d_keys.hpp.  Everything here is __host__ __device__
+// and free of HIP types, so a plain C++ program can include it and test the networks (tests/test_rank_filter_host.py).
 #pragma once
-#include <cstdint>
-
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define B4D_RF_HD __host__ __device__ __forceinline__
-#else
-#define B4D_RF_HD inline
-#endif
-#if defined(__clang__)
-#define B4D_RF_UNROLL _Pragma("unroll")
-#else
-#define B4D_RF_UNROLL
-#endif
+#include "b4d_keys.hpp"
 
 namespace b4d {
-namespace rankfilt {
-
-// np.sort's order as an unsigned integer order: -Inf < ... < -0 < +0 < ... < +Inf < NaN.  Every NaN becomes the positive quiet
-// NaN, whose key lies above +Inf's; negative values have all bits flipped, the others the sign bit set.
-constexpr uint32_t KEY_NAN = 0xFFC00000u;
-B4D_RF_HD uint32_t float_bits(float x) {
-    uint32_t u;
-    __builtin_memcpy(&u, &x, 4);
-    return u;
-}
-B4D_RF_HD float bits_float(uint32_t u) {
-    float x;
-    __builtin_memcpy(&x, &u, 4);
-    return x;
-}
-B4D_RF_HD uint32_t to_key(float x) {
-    uint32_t u = float_bits(x);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) u = 0x7FC00000u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-B4D_RF_HD float from_key(uint32_t k) { return bits_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
-struct KeyOps {
-    typedef uint32_t T;
-    static B4D_RF_HD T lo(T a, T b) { return a < b ? a : b; }
-    static B4D_RF_HD T hi(T a, T b) { return a < b ? b : a; }
-};
+namespace rankfilt {   // (sees namespace keys: b4d_keys.hpp)
 
 template <class O>
-B4D_RF_HD void cex(typename O::T& a, typename O::T& b) {
-    const typename O::T l = O::lo(a, b), h = O::hi(a, b);
-    a = l;
-    b = h;
-}
-template <class O>
-B4D_RF_HD typename O::T med3(typename O::T a, typename O::T b, typename O::T c) {
+B4D_HD typename O::T med3(typename O::T a, typename O::T b, typename O::T c) {
     return O::hi(O::lo(a, b), O::lo(O::hi(a, b), c));
 }
 // a <= b <= c afterwards (3 exchanges)
 template <class O>
-B4D_RF_HD void sort3(typename O::T& a, typename O::T& b, typename O::T& c) {
+B4D_HD void sort3(typename O::T& a, typename O::T& b, typename O::T& c) {
     cex<O>(a, b);
     cex<O>(b, c);
     cex<O>(a, b);
@@ -66,7 +22,7 @@ B4D_RF_HD void sort3(typename O::T& a, typename O::T& b, typename O::T& c) {
 // five elements above them, the two larger column maxima five below, and of the column medians only the middle one can be the
 // median of nine -- so it is med3(max lo, med3 mid, min hi).  A column sort is shared by the three windows the column belongs to.
 template <class O>
-B4D_RF_HD typename O::T median9_sorted_cols(typename O::T l0, typename O::T m0, typename O::T h0, typename O::T l1, typename O::T m1,
+B4D_HD typename O::T median9_sorted_cols(typename O::T l0, typename O::T m0, typename O::T h0, typename O::T l1, typename O::T m1,
                                             typename O::T h1, typename O::T l2, typename O::T m2, typename O::T h2) {
     const typename O::T a = O::hi(O::hi(l0, l1), l2);
     const typename O::T b = med3<O>(m0, m1, m2);
@@ -80,17 +36,17 @@ B4D_RF_HD typename O::T median9_sorted_cols(typename O::T l0, typename O::T m0, 
 // minimum of the front half to v[0] and the maximum of the back half to v[m-1]; the next value takes v[0]'s place and
 // v[m-1] falls off the end.  v is destroyed.  All indices are compile-time after unrolling: v lives in registers.
 template <class O, int N>
-B4D_RF_HD typename O::T median_forgetful(typename O::T (&v)[N]) {
+B4D_HD typename O::T median_forgetful(typename O::T (&v)[N]) {
     static_assert(N % 2 == 1 && N >= 3, "odd N");
     constexpr int M0 = (N + 1) / 2 + 1;
     int nxt = M0 < N ? M0 : N;
-    B4D_RF_UNROLL
+    B4D_HD_UNROLL
     for (int m = (M0 < N ? M0 : N); m >= 3; --m) {
-        B4D_RF_UNROLL
+        B4D_HD_UNROLL
         for (int i = 0; i < m / 2; ++i) cex<O>(v[i], v[m - 1 - i]);
-        B4D_RF_UNROLL
+        B4D_HD_UNROLL
         for (int i = 1; i < (m + 1) / 2; ++i) cex<O>(v[0], v[i]);
-        B4D_RF_UNROLL
+        B4D_HD_UNROLL
         for (int i = m / 2; i < m - 1; ++i) cex<O>(v[i], v[m - 1]);
         if (m > 3) v[0] = v[nxt++];
     }
@@ -99,18 +55,18 @@ B4D_RF_HD typename O::T median_forgetful(typename O::T (&v)[N]) {
 
 // optimal sorting networks of 5 (9 exchanges) and 7 (16 exchanges) values
 template <class O>
-B4D_RF_HD void sort5(typename O::T (&a)[5]) {
+B4D_HD void sort5(typename O::T (&a)[5]) {
     cex<O>(a[0], a[1]); cex<O>(a[3], a[4]); cex<O>(a[2], a[4]); cex<O>(a[2], a[3]); cex<O>(a[1], a[4]);
     cex<O>(a[0], a[3]); cex<O>(a[0], a[2]); cex<O>(a[1], a[3]); cex<O>(a[1], a[2]);
 }
 template <class O>
-B4D_RF_HD void sort7(typename O::T (&a)[7]) {
+B4D_HD void sort7(typename O::T (&a)[7]) {
     cex<O>(a[0], a[6]); cex<O>(a[2], a[3]); cex<O>(a[4], a[5]); cex<O>(a[0], a[2]); cex<O>(a[1], a[4]); cex<O>(a[3], a[6]);
     cex<O>(a[0], a[1]); cex<O>(a[2], a[5]); cex<O>(a[3], a[4]); cex<O>(a[1], a[2]); cex<O>(a[4], a[6]); cex<O>(a[2], a[3]);
     cex<O>(a[4], a[5]); cex<O>(a[1], a[2]); cex<O>(a[3], a[4]); cex<O>(a[5], a[6]);
 }
 template <class O, int S>
-B4D_RF_HD void sort_small(typename O::T (&a)[S]) {
+B4D_HD void sort_small(typename O::T (&a)[S]) {
     static_assert(S == 3 || S == 5 || S == 7, "3, 5 or 7 values");
     if constexpr (S == 3) sort3<O>(a[0], a[1], a[2]);
     if constexpr (S == 5) sort5<O>(a);
@@ -135,38 +91,26 @@ constexpr int rows_kept(int S) {
     return n;
 }
 template <class O, int S>
-B4D_RF_HD typename O::T median_sorted_cols(const typename O::T (&col)[S][S]) {
+B4D_HD typename O::T median_sorted_cols(const typename O::T (&col)[S][S]) {
     constexpr int K = rows_kept(S);
     typename O::T keep[K];
     int n = 0;
-    B4D_RF_UNROLL
+    B4D_HD_UNROLL
     for (int i = 0; i < S; ++i) {
         typename O::T row[S];
-        B4D_RF_UNROLL
+        B4D_HD_UNROLL
         for (int j = 0; j < S; ++j) row[j] = col[j][i];
         sort_small<O, S>(row);
-        B4D_RF_UNROLL
+        B4D_HD_UNROLL
         for (int k = rows_dropped_low(S, i); k < S - rows_dropped_low(S, S - 1 - i); ++k) keep[n++] = row[k];
     }
     return median_forgetful<O, K>(keep);
 }
 
-// rank-th smallest (0-based) of n keys by bitwise selection: the answer is the largest t with #(key < t) <= rank, built from
-// the top bit down.  count(t) returns #(key < t) over the window.  32 counting passes, no sorting, any n.
-template <class Count>
-B4D_RF_HD uint32_t select_bitwise(int rank, Count count) {
-    uint32_t t = 0;
-    for (int bit = 31; bit >= 0; --bit) {
-        const uint32_t trial = t | (1u << bit);
-        if (count(trial) <= rank) t = trial;
-    }
-    return t;
-}
-
 // source index of position i on an axis of n samples under scipy.ndimage's border modes, for any overhang (repeated
 // reflection / wrap); -1 = outside (mode "constant").  Codes as in b4d_warp_*: 0 nearest, 1 reflect, 2 mirror, 3 constant; 4 wrap.
 enum { MODE_NEAREST = 0, MODE_REFLECT = 1, MODE_MIRROR = 2, MODE_CONSTANT = 3, MODE_WRAP = 4 };
-B4D_RF_HD int border_index(int i, int n, int mode) {
+B4D_HD int border_index(int i, int n, int mode) {
     if (i >= 0 && i < n) return i;
     if (mode == MODE_CONSTANT) return -1;
     if (mode == MODE_NEAREST || n == 1) return i < 0 ? 0 : n - 1;

@@ -1,17 +1,82 @@
-// b4d_select.hpp -- exact order statistics of float32 data by 3-pass radix select (11 + 11 + 10 bits)
-// inside one workgroup: LDS histogram, wave-level scan, no sorting.  Keys are the order-preserving
-// unsigned image of the float bits; NaNs are skipped (np.nanpercentile / np.median on finite maps).
+// b4d_select.hpp -- exact order statistics of float32 data by 3-pass radix select (11 + 11 + 10 bits): LDS histogram,
+// wave-level scan, no sorting.  Keys are the order-preserving unsigned image of the float bits (keys::key_bits of
+// b4d_keys.hpp); NaNs are skipped (np.nanpercentile / np.median on finite maps).
+// The three steps of a pass -- count, bin pick, next-larger scan -- are helpers over a strided range (select_count, select_pick,
+// select_next); the kernels that spread a select over many workgroups (k_pctm_* of b4d_stats.hip) are built from them.
+// radix_select / next_larger_key, the one-workgroup form, keep the same steps written out: built from the helpers, the gfx950
+// instruction streams of k_track_fin, k_track_fin2 and k_displace<*> were compared with the written-out form and differed (the
+// same instructions but for an unrolling decision, other registers throughout), and those epilogues are tuned as they stand.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "b4d_keys.hpp"
+#include "b4d_reduce.hpp"
+
 namespace b4d {
 
-__device__ __forceinline__ unsigned f2key(float f) {
-    const unsigned b = __float_as_uint(f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+// visit(x[i]) for the elements first, first + stride, .. of x[0..n): as 16-byte groups where x is 16-byte aligned, the
+// elements behind the last whole group one by one
+template <class Visit>
+__device__ __forceinline__ void select_stream(const float* __restrict__ x, unsigned n, unsigned first, unsigned stride, Visit visit) {
+    const unsigned n4 = ((reinterpret_cast<size_t>(x) & 15) == 0) ? n / 4 : 0;
+    const float4* x4 = reinterpret_cast<const float4*>(x);
+    for (unsigned i = first; i < n4; i += stride) {
+        const float4 a = x4[i];
+        visit(a.x); visit(a.y); visit(a.z); visit(a.w);
+    }
+    for (unsigned j = 4 * n4 + first; j < n; j += stride) visit(x[j]);
 }
-__device__ __forceinline__ float key2f(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+
+// The count pass: hist (REP copies of 2048 LDS words, lanes spread over them by lane % REP) = per digit (key >> sft) & (nb - 1)
+// the number of this workgroup's elements whose key has (key & mask) == prefix.  Whole workgroup; the copies are complete on
+// return (barrier) and still to be added up.
+template <int REP>
+__device__ __forceinline__ void select_count(const float* __restrict__ x, unsigned n, unsigned first, unsigned stride, unsigned mask,
+                                             unsigned prefix, int sft, int nb, unsigned* hist) {
+    for (int i = threadIdx.x; i < 2048 * REP; i += blockDim.x) hist[i] = 0;
+    __syncthreads();
+    unsigned* myhist = hist + (threadIdx.x % REP) * 2048;
+    select_stream(x, n, first, stride, [&](float f) {
+        if (f != f) return;
+        const unsigned key = keys::key_bits(f);
+        if ((key & mask) == prefix) atomicAdd(&myhist[(key >> sft) & (nb - 1)], 1u);
+    });
+    __syncthreads();
+}
+
+// The bin pick, by one wave: lane l adds the bins 32 l .. 32 l + 31 of hist (2048 words), an inclusive wave scan gives every lane
+// the count below its range, rank(total) names the wanted rank among the counted elements, and the lane whose range holds it
+// walks its bins.  That lane alone calls found(bin, count below the bin, count in the bin).
+template <class Rank, class Found>
+__device__ __forceinline__ void select_pick(const unsigned* hist, int lane, Rank rank, Found found) {
+    const int per = 2048 / 64;
+    unsigned s = 0;
+    for (int i = 0; i < per; ++i) s += hist[lane * per + i];
+    const unsigned incl = wave_scan_inclusive(s, lane);
+    const unsigned excl = incl - s, kk = rank(__shfl(incl, 63, 64));
+    if (kk >= excl && kk < incl) {
+        unsigned run = excl;
+        for (int i = 0; i < per; ++i) {
+            const unsigned c = hist[lane * per + i];
+            if (kk < run + c) {
+                found((unsigned)(lane * per + i), run, c);
+                break;
+            }
+            run += c;
+        }
+    }
+}
+
+// The next-larger scan: smallest key strictly greater than `ka` among the non-NaN elements first, first + stride, .. of a
+// wave's lanes (0xffffffff if none); lane 0 holds it.
+__device__ __forceinline__ unsigned select_next(const float* __restrict__ x, unsigned n, unsigned first, unsigned stride, unsigned ka) {
+    unsigned best = 0xffffffffu;
+    select_stream(x, n, first, stride, [&](float f) {
+        if (f != f) return;
+        const unsigned key = keys::key_bits(f);
+        if (key > ka && key < best) best = key;
+    });
+    return wave_min(best);
 }
 
 // k-th smallest (0-based) among the non-NaN elements of x[0..n).  Whole workgroup participates and gets
@@ -39,7 +104,7 @@ __device__ inline unsigned radix_select(const float* __restrict__ x, unsigned n,
         __syncthreads();
         auto visit = [&](float f) {
             if (f != f) return;
-            const unsigned key = f2key(f);
+            const unsigned key = keys::key_bits(f);
             if ((key & mask) == prefix) atomicAdd(&myhist[(key >> sft) & (nb - 1)], 1u);
         };
         // 16-byte loads, two per lane in flight: the pass is a pure stream over the map
@@ -66,11 +131,10 @@ __device__ inline unsigned radix_select(const float* __restrict__ x, unsigned n,
             }
             __syncthreads();
         }
-        if (threadIdx.x < 64) {  // one wave: 32 bins per lane, then a wave scan
+        if (threadIdx.x < 64) {  // one wave: 32 bins per lane, then a wave scan (select_pick, written out: see the head of the file)
             const int per = 2048 / 64;
             unsigned s = 0;
             for (int i = 0; i < per; ++i) s += hist[threadIdx.x * per + i];
-            // (wave_scan_inclusive of b4d_reduce.hpp, kept inline: through the helper the tracking epilogues' instructions come out different)
             unsigned incl = s;
 #pragma unroll
             for (int o = 1; o < 64; o <<= 1) {
@@ -102,7 +166,7 @@ __device__ inline unsigned radix_select(const float* __restrict__ x, unsigned n,
             if (threadIdx.x == 0) sh[3] = 0;
             __syncthreads();
             auto put = [&](float f) {
-                const bool m = (f == f) && ((f2key(f) & mask) == prefix);
+                const bool m = (f == f) && ((keys::key_bits(f) & mask) == prefix);
                 const unsigned long long bal = __ballot(m);
                 if (bal == 0) return;
                 const int lane = threadIdx.x & 63, leader = __ffsll((long long)bal) - 1;
@@ -137,7 +201,7 @@ __device__ inline unsigned next_larger_key(const float* __restrict__ x, unsigned
     unsigned best = 0xffffffffu;
     auto visit = [&](float f) {
         if (f != f) return;
-        const unsigned key = f2key(f);
+        const unsigned key = keys::key_bits(f);
         if (key > ka && key < best) best = key;
     };
     const unsigned n4 = ((reinterpret_cast<size_t>(x) & 15) == 0) ? n / 4 : 0;
@@ -147,7 +211,7 @@ __device__ inline unsigned next_larger_key(const float* __restrict__ x, unsigned
         visit(a.x); visit(a.y); visit(a.z); visit(a.w);
     }
     for (unsigned j = 4 * n4 + threadIdx.x; j < n; j += blockDim.x) visit(x[j]);
-    // (wave_min of b4d_reduce.hpp, kept inline for the same reason)
+    // (select_next's scan and wave_min, written out: see the head of the file)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const unsigned t = __shfl_down(best, o, 64);

@@ -421,8 +421,8 @@ __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ 
         unsigned kb = ka;
         if (hi != lo && nl + ne <= hi) kb = next_larger_key(x, n_all, ka, hist);
         if (threadIdx.x == 0) {
-            o[0] = (double)key2f(ka);
-            o[1] = (double)key2f(kb);
+            o[0] = (double)keys::from_key(ka);
+            o[1] = (double)keys::from_key(kb);
             o[2] = vi - floor(vi);
             o[3] = (double)n;
         }
@@ -449,28 +449,10 @@ __global__ void __launch_bounds__(256) k_pctm_hist(PctMulti p) {
     constexpr int REP = 4;
     __shared__ unsigned hist[2048 * REP];
     const int f = blockIdx.y, j = blockIdx.z;
-    const float* x = p.frames + (size_t)f * p.npix;
-    const unsigned n = (unsigned)p.npix;
     constexpr int sft = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0), nb = PASS == 2 ? 1024 : 2048;
     constexpr unsigned mask = PASS == 0 ? 0u : (PASS == 1 ? 0xffe00000u : 0xfffffc00u);
     const unsigned prefix = PASS == 0 ? 0u : p.state[((size_t)f * p.nq + j) * 8];
-    for (int i = threadIdx.x; i < 2048 * REP; i += 256) hist[i] = 0;
-    __syncthreads();
-    unsigned* my = hist + (threadIdx.x % REP) * 2048;
-    auto visit = [&](float v) {
-        if (v != v) return;
-        const unsigned key = f2key(v);
-        if ((key & mask) == prefix) atomicAdd(&my[(key >> sft) & (nb - 1)], 1u);
-    };
-    const unsigned n4 = ((reinterpret_cast<size_t>(x) & 15) == 0) ? n / 4 : 0;
-    const float4* x4 = reinterpret_cast<const float4*>(x);
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
-        const float4 a = x4[i];
-        visit(a.x); visit(a.y); visit(a.z); visit(a.w);
-    }
-    if (blockIdx.x == 0)
-        for (unsigned i = 4 * n4 + threadIdx.x; i < n; i += 256) visit(x[i]);
-    __syncthreads();
+    select_count<REP>(p.frames + (size_t)f * p.npix, (unsigned)p.npix, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, mask, prefix, sft, nb, hist);
     unsigned* g = p.hist + ((size_t)f * p.nq + j) * 2048;
     for (int i = threadIdx.x; i < 2048; i += 256) {
         unsigned t = 0;
@@ -480,55 +462,33 @@ __global__ void __launch_bounds__(256) k_pctm_hist(PctMulti p) {
     }
 }
 
-// choose the bin of the target rank, update the state, clear the histogram for the next pass.  grid (batch, nq), block 64.
-// PASS 0 reads the shared pass-0 histogram of query 0 and derives n_valid and the rank from q.
+// choose the bin of the target rank, update the state (zero on entry of pass 0), clear the histogram for the next pass.
+// grid (batch, nq), block 64.  PASS 0 reads the shared pass-0 histogram of query 0 and derives n_valid and the rank from q.
 template <int PASS>
 __global__ void __launch_bounds__(64) k_pctm_pick(PctMulti p) {
     const int f = blockIdx.x, j = blockIdx.y, lane = threadIdx.x;
     unsigned* st = p.state + ((size_t)f * p.nq + j) * 8;
-    unsigned* g = p.hist + ((size_t)f * p.nq + (PASS == 0 ? 0 : j)) * 2048;
+    const unsigned* g = p.hist + ((size_t)f * p.nq + (PASS == 0 ? 0 : j)) * 2048;
     constexpr int sft = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
-    const int per = 2048 / 64;
-    unsigned s = 0;
-    for (int i = 0; i < per; ++i) s += g[lane * per + i];
-    const unsigned incl = wave_scan_inclusive(s, lane);
-    const unsigned total = __shfl(incl, 63, 64);
-    unsigned kk;
-    if (PASS == 0) {
-        const unsigned n = total;
-        unsigned lo = 0;
-        if (n > 0) lo = pct_rank(pct_virtual_index(p.q[j], n), n);
-        kk = lo;
+    auto rank = [&](unsigned n) {
+        if (PASS != 0) return st[2] - st[1];
+        const unsigned lo = n > 0 ? pct_rank(pct_virtual_index(p.q[j], n), n) : 0u;
         if (lane == 0) {
-            st[0] = 0;
-            st[1] = 0;
             st[2] = lo;
             st[4] = n;
             st[5] = 0xffffffffu;
         }
-    } else {
-        kk = st[2] - st[1];
-    }
+        return lo;
+    };
+    select_pick(g, lane, rank, [&](unsigned bin, unsigned run, unsigned c) {
+        st[0] |= bin << sft;
+        st[1] += run;
+        st[3] = c;
+    });
     __syncthreads();
-    const unsigned excl = incl - s;
-    if (total > 0 && kk >= excl && kk < incl) {
-        unsigned run = excl;
-        for (int i = 0; i < per; ++i) {
-            const unsigned c = g[lane * per + i];
-            if (kk < run + c) {
-                st[0] |= (unsigned)(lane * per + i) << sft;
-                st[1] += run;
-                st[3] = c;
-                break;
-            }
-            run += c;
-        }
-    }
-    __syncthreads();
-    if (PASS != 0 || j == gridDim.y - 1 || true) {   // every query's own histogram slot is cleared for the next pass
+    if (PASS != 0 || j != 0) {   // every query's own histogram slot is cleared for the next pass (slot 0 of pass 0: k_pctm_clear0)
         unsigned* mine = p.hist + ((size_t)f * p.nq + j) * 2048;
-        if (PASS != 0 || j != 0)
-            for (int i = lane; i < 2048; i += 64) mine[i] = 0;
+        for (int i = lane; i < 2048; i += 64) mine[i] = 0;
     }
 }
 
@@ -542,18 +502,8 @@ __global__ void __launch_bounds__(256) k_pctm_clear0(PctMulti p) {
 __global__ void __launch_bounds__(256) k_pctm_next(PctMulti p) {
     __shared__ unsigned sh[4];
     const int f = blockIdx.y, j = blockIdx.z;
-    const float* x = p.frames + (size_t)f * p.npix;
-    const unsigned n = (unsigned)p.npix;
     unsigned* st = p.state + ((size_t)f * p.nq + j) * 8;
-    const unsigned ka = st[0];
-    unsigned best = 0xffffffffu;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const float v = x[i];
-        if (v != v) continue;
-        const unsigned key = f2key(v);
-        if (key > ka && key < best) best = key;
-    }
-    best = wave_min(best);
+    unsigned best = select_next(p.frames + (size_t)f * p.npix, (unsigned)p.npix, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256, st[0]);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -579,8 +529,8 @@ __global__ void __launch_bounds__(64) k_pctm_out(PctMulti p) {
     const unsigned lo = st[2], hi = lo + 1 < n ? lo + 1 : n - 1;
     unsigned kb = st[0];
     if (hi != lo && st[1] + st[3] <= hi && st[5] != 0xffffffffu) kb = st[5];
-    o[0] = (double)key2f(st[0]);
-    o[1] = (double)key2f(kb);
+    o[0] = (double)keys::from_key(st[0]);
+    o[1] = (double)keys::from_key(kb);
     o[2] = vi - floor(vi);
     o[3] = (double)n;
 }

@@ -410,7 +410,6 @@ __global__ void __launch_bounds__(1024) k_step_update(const double* __restrict__
     }
 }
 
-static bool st_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 template <int TMAX>
 static int st_launch_frames(bool vec, int nb, hipStream_t st, const float* stack, int T, size_t npix, const StCalTables& tab, double sat,
@@ -443,7 +442,7 @@ extern "C" int b4d_stepping_fit(const float* stack, int n, int T, long long npix
         tab.Ginv[i] = gram_inv ? gram_inv[i] : 0.0;
     }
     const size_t np = (size_t)npix;
-    const bool vec = (np & 3) == 0 && st_aligned(stack, 16) && st_aligned(coeff, 16) && st_aligned(residual, 16) && st_aligned(n_samples, 4);
+    const bool vec = (np & 3) == 0 && ptr_aligned(stack, 16) && ptr_aligned(coeff, 16) && ptr_aligned(residual, 16) && ptr_aligned(n_samples, 4);
     const size_t blocks = (np / (vec ? 4 : 1) + ST_THREADS - 1) / ST_THREADS;
     if (blocks > 0x7fffffffull) return fail(B4D_ESIZE, "stepping: scan too large");
     const dim3 grid((unsigned)blocks, (unsigned)n), block(ST_THREADS);
@@ -495,7 +494,7 @@ extern "C" int b4d_stepping_calibrate_step(const float* stack, int T, long long 
         if (!std::isfinite(i < 3 * T ? basis[i] : i < 3 * T + 9 ? gram_inv[i - 3 * T] : delta[i - 3 * T - 9]))
             return fail(B4D_EINVAL, "stepping: the tables must be finite");
     const size_t np = (size_t)npix;
-    const bool vec = (np & 3) == 0 && st_aligned(stack, 16);
+    const bool vec = (np & 3) == 0 && ptr_aligned(stack, 16);
     const size_t want = (np / (vec ? 4 : 1) + ST_THREADS - 1) / ST_THREADS;
     const int nb = (int)std::min<size_t>(want, ST_CAL_MAX_BLOCKS);
     const int tmax = T <= 8 ? 8 : T <= 16 ? 16 : 32;

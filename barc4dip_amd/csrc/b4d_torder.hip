@@ -1,10 +1,10 @@
 // b4d_torder.hip -- per-pixel order statistics along the frame axis of a stack (barc4dip_amd.metrics.order,
 // barc4dip_amd.preprocessing.combine): quantiles with NumPy's methods linear / lower / higher / nearest /
 // midpoint under the NaN policies "propagate" and "omit", and a robust mean that rejects samples by their distance from the
-// per-pixel median (absolute, MAD or Poisson scale; the rules of b4d_despeckle along T instead of over a window).
+// per-pixel median (absolute, MAD or Poisson scale; the outlier rule of b4d_keys.hpp, which b4d_despeckle applies over a window).
 //
 // Semantics.  A stack is (T, npix) float32, frames frame_stride elements apart.  Per pixel the samples are sorted in np.sort's
-// order (to_key of b4d_rankfilt.hpp: NaN above +Inf).  With s[0 .. n) the sorted samples that take part, q in [0, 1] and
+// order (to_key of b4d_keys.hpp: NaN above +Inf).  With s[0 .. n) the sorted samples that take part, q in [0, 1] and
 // h = q (n - 1) in float64, quantile_position (b4d_sortnet.hpp) gives the index i and the fraction g of the method; g == 0 gives
 // s[i] itself, otherwise (float) (a + (b - a) g) with a = (double) s[i], b = (double) s[i + 1], the difference, product and sum
 // each rounded once in float64.  Selections are exact, so both routes below give the same bits.
@@ -30,7 +30,7 @@
 
 namespace b4d {
 
-using namespace rankfilt;
+using namespace keys;
 using sortnet::quantile_position;
 
 constexpr int TO_THREADS = 256;
@@ -43,17 +43,9 @@ struct QuantArgs {
     double q[TO_MAX_Q];
     int n_q, method, nan_policy;
 };
-struct RobustArgs {
-    int scale_kind;    // 0 absolute, 1 mad, 2 poisson
-    float threshold;   // poisson: threshold * threshold, formed in float32 on the host
-    float min_scale;
-    int polarity;      // 0 both, 1 hot, 2 dead
-};
 
 __device__ __forceinline__ float to_nan() { return bits_float(0x7FC00000u); }
 __device__ __forceinline__ bool to_finite(float x) { return (float_bits(x) & 0x7F800000u) != 0x7F800000u; }
-// np.maximum(s, floor): NaN stays NaN
-__device__ __forceinline__ float to_max_keep_nan(float s, float floor_) { return s < floor_ ? floor_ : s; }
 
 // the value between the sorted keys ka <= kb at fraction g
 __device__ __forceinline__ float to_interpolate(uint32_t ka, uint32_t kb, double g) {
@@ -67,20 +59,6 @@ __device__ __forceinline__ float to_interpolate(uint32_t ka, uint32_t kb, double
 __device__ __forceinline__ void to_median_position(int n, int& i, double& g) {
     i = n > 0 ? (n - 1) >> 1 : 0;
     g = (n > 0 && (n & 1) == 0) ? 0.5 : 0.0;
-}
-
-// right-hand side of the rejection test (the `scale` output) and the test itself, in b4d_despeckle's float32 operation order
-__device__ __forceinline__ float to_rhs(const RobustArgs& a, float med, float mad) {
-    if (a.scale_kind == 1) return __fmul_rn(a.threshold, to_max_keep_nan(__fmul_rn(1.4826f, mad), a.min_scale));
-    if (a.scale_kind == 2) return __fmul_rn(a.threshold, to_max_keep_nan(med, a.min_scale));
-    return a.threshold;
-}
-__device__ __forceinline__ bool to_rejected(const RobustArgs& a, float x, float med, float rhs) {
-    const float d = __fsub_rn(x, med);
-    bool o = a.scale_kind == 2 ? __fmul_rn(d, d) > rhs : fabsf(d) > rhs;
-    if (a.polarity == 1) o = o && d > 0.f;
-    if (a.polarity == 2) o = o && d < 0.f;
-    return o || !to_finite(x);     // a sample that is not finite takes no part
 }
 
 // ------------------------------------------------------------------------------------------------ register route
@@ -197,7 +175,7 @@ __global__ void __launch_bounds__(TO_THREADS) k_tq_reg(const float* __restrict__
 }
 
 template <int TP, int PPL, bool VEC>
-__global__ void __launch_bounds__(TO_THREADS) k_tr_reg(const float* __restrict__ stack, int T, size_t fs, size_t npix, RobustArgs a,
+__global__ void __launch_bounds__(TO_THREADS) k_tr_reg(const float* __restrict__ stack, int T, size_t fs, size_t npix, OutlierRule a,
                                                        float* __restrict__ mean, float* __restrict__ median, float* __restrict__ scale,
                                                        unsigned short* __restrict__ n_kept, unsigned char* __restrict__ rejected,
                                                        float* __restrict__ cleaned, size_t os) {
@@ -246,11 +224,11 @@ __global__ void __launch_bounds__(TO_THREADS) k_tr_reg(const float* __restrict__
 #pragma unroll
             for (int t = 0; t < TP; ++t) k[j][t] = t < T ? to_key(fabsf(__fsub_rn(x[j][t], med[j]))) : KEY_PAD;
             sortnet::sortnet<KeyOps, TP>(k[j]);
-            rhs[j] = to_rhs(a, med[j], to_sorted_median<TP>(k[j], nn[j]));
+            rhs[j] = outlier_rhs(a, med[j], to_sorted_median<TP>(k[j], nn[j]));
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < PPL; ++j) rhs[j] = to_rhs(a, med[j], 0.f);
+        for (int j = 0; j < PPL; ++j) rhs[j] = outlier_rhs(a, med[j], 0.f);
     }
     // the kept samples are added in TO_GROUP partial sums, partial s over t = s, s + 8, .. in ascending t, joined as
     // ((P0 + P1) + (P2 + P3)) + ((P4 + P5) + (P6 + P7)): the order of the general route's lanes and butterfly
@@ -269,7 +247,7 @@ __global__ void __launch_bounds__(TO_THREADS) k_tr_reg(const float* __restrict__
             float cl[PPL];
 #pragma unroll
             for (int j = 0; j < PPL; ++j) {
-                const bool o = to_rejected(a, x[j][t], med[j], rhs[j]);
+                const bool o = outlier_rejected(a, x[j][t], med[j], rhs[j]);
                 rj[j] = o ? 1 : 0;
                 cl[j] = o ? med[j] : x[j][t];
                 acc[j][t % TO_GROUP] += o ? 0.0 : (double)x[j][t];
@@ -404,7 +382,7 @@ __global__ void __launch_bounds__(TO_THREADS) k_tq_gen(const float* __restrict__
 }
 
 template <int KPL>
-__global__ void __launch_bounds__(TO_THREADS) k_tr_gen(const float* __restrict__ stack, int T, size_t fs, size_t npix, RobustArgs a,
+__global__ void __launch_bounds__(TO_THREADS) k_tr_gen(const float* __restrict__ stack, int T, size_t fs, size_t npix, OutlierRule a,
                                                        float* __restrict__ mean, float* __restrict__ median, float* __restrict__ scale,
                                                        unsigned short* __restrict__ n_kept, unsigned char* __restrict__ rejected,
                                                        float* __restrict__ cleaned, size_t os) {
@@ -422,12 +400,12 @@ __global__ void __launch_bounds__(TO_THREADS) k_tr_gen(const float* __restrict__
     float mad = 0.f;
     if (a.scale_kind == 1)      // the keys of |x - med|, formed on the fly
         mad = tg_median<KPL>(n, [&](int m) { return kk[m] == KEY_PAD ? KEY_PAD : to_key(fabsf(__fsub_rn(from_key(kk[m]), med))); });
-    const float rhs = to_rhs(a, med, mad);
+    const float rhs = outlier_rhs(a, med, mad);
     double acc = 0.0;      // partial `sub` of the kept samples, ascending t
     int kept = 0;
     for (int t = sub; t < T; t += TO_GROUP) {      // the last pass reads the tile again: a rolled loop, the key registers are free
         const float x = from_key(to_lds[tg_slot(t, p)]);
-        const bool o = to_rejected(a, x, med, rhs);
+        const bool o = outlier_rejected(a, x, med, rhs);
         acc += o ? 0.0 : (double)x;
         kept += o ? 0 : 1;
         if (rejected && inside) rejected[(size_t)t * os + pix] = o ? 1 : 0;
@@ -444,11 +422,6 @@ __global__ void __launch_bounds__(TO_THREADS) k_tr_gen(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static bool to_overlaps(const void* a, size_t abytes, const void* b, size_t bbytes) {
-    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-    return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
-}
-static bool to_aligned(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
 constexpr long long TO_MAX_NPIX = (long long)1 << 36;   // 2^31 tiles of the general route
 
 // pixels per lane of the register route by padded length (the resource table)
@@ -457,18 +430,18 @@ template <int TP> struct ToPpl { static constexpr int quant = TP <= 16 ? 4 : (TP
 template <int TP>
 static int launch_tq_reg(const float* stack, int T, size_t fs, size_t npix, const QuantArgs& a, float* out, unsigned short* nv, hipStream_t st) {
     constexpr int PPL = ToPpl<TP>::quant;
-    const bool vec = PPL > 1 && npix % PPL == 0 && fs % PPL == 0 && to_aligned(stack, 4 * PPL) && to_aligned(out, 4 * PPL) && to_aligned(nv, 2 * PPL);
+    const bool vec = PPL > 1 && npix % PPL == 0 && fs % PPL == 0 && ptr_aligned(stack, 4 * PPL) && ptr_aligned(out, 4 * PPL) && ptr_aligned(nv, 2 * PPL);
     const dim3 grid((unsigned)((npix + (size_t)PPL * TO_THREADS - 1) / ((size_t)PPL * TO_THREADS)));
     if (vec) return launch(k_tq_reg<TP, PPL, true>, grid, dim3(TO_THREADS), 0, st, stack, T, fs, npix, a, out, nv);
     return launch(k_tq_reg<TP, PPL, false>, grid, dim3(TO_THREADS), 0, st, stack, T, fs, npix, a, out, nv);
 }
 template <int TP>
-static int launch_tr_reg(const float* stack, int T, size_t fs, size_t npix, const RobustArgs& a, float* mean, float* median, float* scale,
+static int launch_tr_reg(const float* stack, int T, size_t fs, size_t npix, const OutlierRule& a, float* mean, float* median, float* scale,
                          unsigned short* nk, unsigned char* rej, float* cleaned, size_t os, hipStream_t st) {
     constexpr int PPL = ToPpl<TP>::robust;
-    const bool vec = PPL > 1 && npix % PPL == 0 && fs % PPL == 0 && os % PPL == 0 && to_aligned(stack, 4 * PPL) && to_aligned(mean, 4 * PPL) &&
-                     to_aligned(median, 4 * PPL) && to_aligned(scale, 4 * PPL) && to_aligned(nk, 2 * PPL) && to_aligned(rej, PPL) &&
-                     to_aligned(cleaned, 4 * PPL);
+    const bool vec = PPL > 1 && npix % PPL == 0 && fs % PPL == 0 && os % PPL == 0 && ptr_aligned(stack, 4 * PPL) && ptr_aligned(mean, 4 * PPL) &&
+                     ptr_aligned(median, 4 * PPL) && ptr_aligned(scale, 4 * PPL) && ptr_aligned(nk, 2 * PPL) && ptr_aligned(rej, PPL) &&
+                     ptr_aligned(cleaned, 4 * PPL);
     const dim3 grid((unsigned)((npix + (size_t)PPL * TO_THREADS - 1) / ((size_t)PPL * TO_THREADS)));
     if (vec) return launch(k_tr_reg<TP, PPL, true>, grid, dim3(TO_THREADS), 0, st, stack, T, fs, npix, a, mean, median, scale, nk, rej, cleaned, os);
     return launch(k_tr_reg<TP, PPL, false>, grid, dim3(TO_THREADS), 0, st, stack, T, fs, npix, a, mean, median, scale, nk, rej, cleaned, os);
@@ -495,7 +468,7 @@ extern "C" int b4d_temporal_quantiles(const float* stack, int T, long long frame
     }
     a.n_q = n_q, a.method = method, a.nan_policy = nan_policy;
     const size_t fs = (size_t)frame_stride, np = (size_t)npix, sbytes = ((size_t)(T - 1) * fs + np) * sizeof(float);
-    if (to_overlaps(stack, sbytes, out, (size_t)n_q * np * sizeof(float)) || to_overlaps(stack, sbytes, n_valid, np * sizeof(unsigned short)))
+    if (ranges_overlap(stack, sbytes, out, (size_t)n_q * np * sizeof(float)) || ranges_overlap(stack, sbytes, n_valid, np * sizeof(unsigned short)))
         return fail(B4D_EINVAL, "b4d_temporal_quantiles: an output overlaps the stack");
     hipStream_t st = (hipStream_t)stream;
     if (T > TO_MAX_REG_T || (flags & 1)) {
@@ -524,14 +497,10 @@ extern "C" int b4d_temporal_robust_mean(const float* stack, int T, long long fra
     if (!(threshold >= 0.f) || !(min_scale >= 0.f)) return fail(B4D_EINVAL, "b4d_temporal_robust_mean: threshold and min_scale must be >= 0");
     const size_t fs = (size_t)frame_stride, os = (size_t)out_stride, np = (size_t)npix;
     const size_t sbytes = ((size_t)(T - 1) * fs + np) * sizeof(float), obytes = (size_t)(T - 1) * os + np;
-    if (to_overlaps(stack, sbytes, mean, np * 4) || to_overlaps(stack, sbytes, median, np * 4) || to_overlaps(stack, sbytes, scale, np * 4) ||
-        to_overlaps(stack, sbytes, n_kept, np * 2) || to_overlaps(stack, sbytes, rejected, obytes) || to_overlaps(stack, sbytes, cleaned, obytes * 4))
+    if (ranges_overlap(stack, sbytes, mean, np * 4) || ranges_overlap(stack, sbytes, median, np * 4) || ranges_overlap(stack, sbytes, scale, np * 4) ||
+        ranges_overlap(stack, sbytes, n_kept, np * 2) || ranges_overlap(stack, sbytes, rejected, obytes) || ranges_overlap(stack, sbytes, cleaned, obytes * 4))
         return fail(B4D_EINVAL, "b4d_temporal_robust_mean: an output overlaps the stack");
-    RobustArgs a;
-    a.scale_kind = scale_kind;
-    a.threshold = scale_kind == 2 ? threshold * threshold : threshold;
-    a.min_scale = min_scale;
-    a.polarity = polarity;
+    const OutlierRule a = make_outlier_rule(scale_kind, threshold, min_scale, polarity);
     hipStream_t st = (hipStream_t)stream;
     if (T > TO_MAX_REG_T || (flags & 1)) {
         const dim3 grid((unsigned)((np + TO_TILE - 1) / TO_TILE));

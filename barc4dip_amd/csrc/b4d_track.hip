@@ -269,7 +269,7 @@ __device__ __forceinline__ unsigned lower_middle(unsigned n) { return (n & 1u) ?
 // search is needed and `full` is null.  Whole workgroup; hist: 16 LDS words.
 __device__ inline bool median_from_select(unsigned ka, unsigned n, unsigned nl, unsigned ne, const float* cx, unsigned cn,
                                           const float* full, unsigned* hist, float& med) {
-    const float a = key2f(ka);
+    const float a = keys::from_key(ka);
     float b = a;
     if (!(n & 1u) && nl + ne <= n / 2) {
         unsigned kb = next_larger_key(cx, cn, ka, hist);
@@ -277,7 +277,7 @@ __device__ inline bool median_from_select(unsigned ka, unsigned n, unsigned nl, 
             if (!full) return false;
             kb = next_larger_key(full, n, ka, hist);
         }
-        b = key2f(kb);
+        b = keys::from_key(kb);
     }
     med = (n & 1u) ? a : __fmul_rn(__fadd_rn(a, b), 0.5f);
     return true;
@@ -665,7 +665,7 @@ __global__ void __launch_bounds__(256) k_ncc_sample(NccArgs p, unsigned* __restr
             for (int b = 0; b < 16; ++b) {
                 const unsigned c = hist[16 * threadIdx.x + b];
                 if (k < below + c) {
-                    pred[pair] = 1024u + 16u * threadIdx.x + (unsigned)b;   // f2key of a non-negative float: bits | 0x80000000
+                    pred[pair] = 1024u + 16u * threadIdx.x + (unsigned)b;   // keys::key_bits(a) >> 21 of a non-negative a: (bits | 0x80000000) >> 21
                     break;
                 }
                 below += c;

@@ -527,7 +527,7 @@ __global__ void __launch_bounds__(WMR_Q* MX::LANES) k_wmr_rows_mag(const float2*
         float bv = -1.0f;
         int bi = 0x7fffffff;
         unsigned cnt = 0, low = 0;   // elements of this lane inside / below the bin the median is expected in (b4d_track.hip)
-        auto kbin = [](float m) { return (__float_as_uint(m) | 0x80000000u) >> 21; };   // f2key(m >= 0) >> 21
+        auto kbin = [](float m) { return (__float_as_uint(m) | 0x80000000u) >> 21; };   // keys::key_bits(m) >> 21 of m >= 0: no sign test
         typename MX::template PosIter<L> pk_it(ltq);
         for (int x = ltq; x < g.W; x += L) {
             const float2 z = bufq[pk_it.pos()];

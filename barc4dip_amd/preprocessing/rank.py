@@ -16,10 +16,9 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from ..metrics.order import _robust_args      # the outlier rule's arguments: one check for the window and the stack form
 
 _MODES = {"nearest": 0, "reflect": 1, "mirror": 2, "constant": 3, "grid-constant": 3, "wrap": 4, "grid-wrap": 4}
-_SCALES = {"absolute": 0, "mad": 1, "poisson": 2}
-_POLARITIES = {"both": 0, "hot": 1, "dead": 2}
 MAX_SIZE = 15
 
 
@@ -120,12 +119,7 @@ def remove_outliers(images, size: int = 3, *, threshold: float = 6.0, scale: str
     "count": int64 (T,) replaced pixels per frame}``."""
     if np.ndim(size) != 0 or size not in (3, 5, 7):
         raise ValueError(f"size must be 3, 5 or 7; got {size!r}")
-    if scale not in _SCALES:
-        raise ValueError(f"Invalid scale option: {scale!r} (expected one of {sorted(_SCALES)})")
-    if polarity not in _POLARITIES:
-        raise ValueError(f"Invalid polarity: {polarity!r} (expected one of {sorted(_POLARITIES)})")
-    if not float(threshold) >= 0.0 or not float(min_scale) >= 0.0:
-        raise ValueError("threshold and min_scale must be >= 0")
+    kind, thr, floor_, pol = _robust_args(threshold, scale, polarity, min_scale)
     m = _mode(mode)
     torch = _ffi.require_gpu()
     t, batch, ny, nx = _frames(images)
@@ -133,8 +127,7 @@ def remove_outliers(images, size: int = 3, *, threshold: float = 6.0, scale: str
     mask = torch.empty(tuple(t.shape), dtype=torch.uint8, device=t.device) if return_mask else None
     count = torch.empty((batch,), dtype=torch.int64, device=t.device) if return_mask else None
     null = C.c_void_p(0)
-    _ffi.check(_ffi.lib().b4d_despeckle(D.ptr(t), batch, ny, nx, int(size), _SCALES[scale], float(threshold), float(min_scale),
-                                        _POLARITIES[polarity], m, float(cval), D.ptr(out), D.ptr(mask) if return_mask else null,
+    _ffi.check(_ffi.lib().b4d_despeckle(D.ptr(t), batch, ny, nx, int(size), kind, thr, floor_, pol, m, float(cval), D.ptr(out), D.ptr(mask) if return_mask else null,
                                         D.ptr(count) if return_mask else null, _ffi.stream_ptr()))
     frames = out if return_tensors else D.to_host(out)
     if not return_mask:

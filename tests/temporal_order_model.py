@@ -65,25 +65,30 @@ def median(stack, ignore_nan=False):
     return quantiles(stack, [0.5], "midpoint", ignore_nan)[0][0]
 
 
-def robust_mean(stack, threshold=5.0, scale="mad", polarity="both", min_scale=0.0):
-    """{"mean", "median", "scale", "n_kept", "rejected", "cleaned"} in the float32 operation order of the kernels."""
-    x = np.asarray(stack).astype(np.float32)
-    finite = np.isfinite(x)
-    x = np.where(finite, x, np.float32(np.nan)).astype(np.float32)
+def outlier_rule(x, med, mad, threshold=5.0, scale="mad", polarity="both", min_scale=0.0):
+    """(rhs, rejected) of the outlier rule (csrc/b4d_keys.hpp: outlier_rhs, outlier_rejected) for float32 samples x against the
+    median med of their neighbourhood -- a window (remove_outliers) or the frames of a stack (robust_mean) -- and, for
+    scale="mad" only, its MAD (a callable is evaluated only then).  Every float32 operation is rounded on its own; x, med and mad
+    broadcast, rhs has the shape of med."""
+    x, med = np.asarray(x), np.asarray(med)
+    assert x.dtype == np.float32 and med.dtype == np.float32
     thr, floor_ = np.float32(threshold), np.float32(min_scale)
+
+    def floored(s):      # np.maximum(s, floor_) with the tie -0 / +0 pinned (NumPy returns either operand): s unless s < floor_
+        return np.where(s < floor_, floor_, s)
+
     with np.errstate(all="ignore"):
-        med = median(x, ignore_nan=True)
-        d = x - med[None]
-        assert d.dtype == np.float32
+        d = x - med
         if scale == "absolute":
             rhs = np.full_like(med, thr)
             out = np.abs(d) > rhs
         elif scale == "mad":
-            mad = median(np.abs(d), ignore_nan=True)
-            rhs = thr * np.maximum(np.float32(1.4826) * mad, floor_)
+            mad = np.asarray(mad() if callable(mad) else mad)
+            assert mad.dtype == np.float32
+            rhs = thr * floored(np.float32(1.4826) * mad)
             out = np.abs(d) > rhs
         elif scale == "poisson":
-            rhs = (thr * thr) * np.maximum(med, floor_)
+            rhs = (thr * thr) * floored(med)
             out = d * d > rhs
         else:
             raise ValueError(scale)
@@ -93,7 +98,18 @@ def robust_mean(stack, threshold=5.0, scale="mad", polarity="both", min_scale=0.
             out &= d < 0
         elif polarity != "both":
             raise ValueError(polarity)
-        out |= ~finite
+        out |= ~np.isfinite(x)          # last: a sample that is not finite is always an outlier
+    assert d.dtype == np.float32 and rhs.dtype == np.float32
+    return rhs, out
+
+
+def robust_mean(stack, threshold=5.0, scale="mad", polarity="both", min_scale=0.0):
+    """{"mean", "median", "scale", "n_kept", "rejected", "cleaned"} in the float32 operation order of the kernels."""
+    x = np.asarray(stack).astype(np.float32)
+    x = np.where(np.isfinite(x), x, np.float32(np.nan)).astype(np.float32)
+    with np.errstate(all="ignore"):
+        med = median(x, ignore_nan=True)
+        rhs, out = outlier_rule(x, med, lambda: median(np.abs(x - med[None]), ignore_nan=True), threshold, scale, polarity, min_scale)
         n_kept = np.count_nonzero(~out, axis=0)
         total = np.sum(np.where(out, 0.0, x.astype(np.float64)), axis=0)
         mean = np.where(n_kept > 0, total / np.maximum(n_kept, 1), np.nan).astype(np.float32)

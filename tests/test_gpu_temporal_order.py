@@ -373,3 +373,40 @@ def test_g_cabi_misuse_returns_einval(env):
     torch.cuda.synchronize()                                    # and the same calls with good arguments run
     assert same(out[0].cpu().numpy(), M.quantiles(x.reshape(T, npix), [0.5], "linear")[0][0]) and bool((out[1:] == -7.0).all())
     assert same(f[1].cpu().numpy(), M.median(x.reshape(T, npix)))
+
+
+# ------------------------------------------------------------------------------------------------ one outlier rule
+def window_stack(image, size):
+    """(size * size, H, W): frame dy * size + dx holds, for every pixel, the element (dy, dx) of its reflect-mode size x size
+    window; frame size * size // 2 is the image.  Along T a pixel has the samples remove_outliers sees in its window."""
+    r = size // 2
+    p = np.pad(image, r, mode="symmetric")
+    H, W = image.shape
+    return np.stack([p[dy:dy + H, dx:dx + W] for dy in range(size) for dx in range(size)]).astype(np.float32)
+
+
+def test_spatial_and_temporal_units_apply_one_rule(env):
+    """remove_outliers on an image and temporal_robust_mean (both routes) on the stack of the image's window offsets see the same
+    samples per pixel, so the one rule of b4d_keys.hpp must give the same decision and the same repaired value, bit for bit: the
+    mask equals rejected[centre] and the repaired frame equals cleaned[centre].  13 x 17 Poisson(50) counts with planted 4000
+    (corner), 900 (edge), 0, 1 (interior) and 51.5 (corner); sizes 3 and 5; every scale, polarity and three settings."""
+    img = np.random.default_rng(50).poisson(50, (13, 17)).astype(np.float32)
+    img[0, 0], img[0, 8], img[6, 6], img[9, 12], img[12, 16] = 4000.0, 900.0, 0.0, 1.0, 51.5
+    for size in (3, 5):
+        stack, c = window_stack(img, size), size * size // 2
+        assert stack.shape == (size * size, 13, 17) and same(stack[c], img)
+        flagged = dict.fromkeys(M.SCALES, 0)
+        for scale in M.SCALES:
+            for polarity in M.POLARITIES:
+                for threshold, min_scale in ((5.0, 0.0), (3.0, 1.0), (20.0, 0.0)):
+                    what = (size, scale, polarity, threshold, min_scale)
+                    out, info = env.P.remove_outliers(img, size, threshold=threshold, scale=scale, polarity=polarity, min_scale=min_scale,
+                                                      return_mask=True)
+                    flagged[scale] += int(info["mask"].sum())
+                    for general in (False, True):
+                        got = robust_outputs(env, stack, scale, polarity, threshold, min_scale, general=general)
+                        assert same(info["mask"], got["rejected"][c].astype(bool)), (what, general)
+                        assert out.dtype == np.float32 and got["cleaned"].dtype == np.float32, (what, general)
+                        assert np.array_equal(out.view(np.uint32), got["cleaned"][c].view(np.uint32)), (what, general)
+        print(f"size {size}: flagged pixels per scale {flagged}")
+        assert all(0 < n < 9 * img.size for n in flagged.values()), flagged

@@ -15,6 +15,8 @@ import pytest
 import scipy.ndimage as ndi
 from numpy.lib.stride_tricks import sliding_window_view
 
+from temporal_order_model import outlier_rule
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MODES = ["reflect", "constant", "nearest", "mirror", "wrap"]
 _PAD = {"reflect": "symmetric", "mirror": "reflect", "nearest": "edge", "wrap": "wrap", "constant": "constant"}
@@ -64,26 +66,11 @@ def model_remove_outliers(images, size=3, threshold=6.0, scale="mad", polarity="
     if a.ndim == 3:
         parts = [model_remove_outliers(f, size, threshold, scale, polarity, min_scale, mode, cval) for f in a]
         return np.stack([p[0] for p in parts]), np.stack([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
-    thr, floor_ = np.float32(threshold), np.float32(min_scale)
     with np.errstate(all="ignore"):
         win = sorted_windows(a, size, mode, cval)
         med = win[..., win.shape[-1] // 2]
-        d = a - med
-        if scale == "absolute":
-            out = np.abs(d) > thr
-        elif scale == "mad":
-            mad = np.sort(np.abs(win - med[..., None]), axis=-1)[..., win.shape[-1] // 2]
-            out = np.abs(d) > thr * np.maximum(np.float32(1.4826) * mad, floor_)
-        elif scale == "poisson":
-            out = d * d > (thr * thr) * np.maximum(med, floor_)
-        else:
-            raise ValueError(scale)
-        if polarity == "hot":
-            out &= d > 0
-        elif polarity == "dead":
-            out &= d < 0
-        out |= ~np.isfinite(a)
-    assert d.dtype == np.float32
+        mad = lambda: np.sort(np.abs(win - med[..., None]), axis=-1)[..., win.shape[-1] // 2]
+        _, out = outlier_rule(a, med, mad, threshold, scale, polarity, min_scale)
     return np.where(out, med, a).astype(np.float32), out, np.array([np.count_nonzero(out)], dtype=np.int64)
 
 
@@ -418,6 +405,17 @@ int main(int argc, char** argv) {
                 for (int i = -20; i < n + 20; ++i) std::printf("%d %d %d %d\n", n, mode, i, border_index(i, n, mode));
         return 0;
     }
+    if (argc > 2 && !std::strcmp(argv[1], "keys")) {        // key table for the Python side: bits, to_key, key_bits, bits of from_key(to_key)
+        std::FILE* f = std::fopen(argv[2], "r");
+        if (!f) return 2;
+        unsigned u;
+        while (std::fscanf(f, "%x", &u) == 1) {
+            const float x = bits_float(u);
+            std::printf("%08x %08x %08x %08x\n", u, to_key(x), key_bits(x), float_bits(from_key(to_key(x))));
+        }
+        std::fclose(f);
+        return 0;
+    }
     std::mt19937_64 rng(12345);
     long bad = keys_and_bitwise(rng);
     bad += exhaustive<9, Cols9>("median9 (sorted columns)");
@@ -478,6 +476,33 @@ def test_border_index_equals_numpy_pad(network_program):
             kw = {"constant_values": -1} if mode == "constant" else {}
             want = np.pad(np.arange(n), (20, 20), mode=_PAD[mode], **kw)
             assert np.array_equal(sel[:, 2], np.arange(-20, n + 20)) and np.array_equal(sel[:, 3], want), (n, mode)
+
+
+def test_float_keys_follow_numpy_sort(network_program, tmp_path):
+    """The float-to-key map of b4d_keys.hpp on +-0, the extreme denormals and normals, +-1, +-Inf, quiet and signalling NaNs of
+    both signs with payloads and 4096 random bit patterns: to_key orders as np.sort does (ties between NaNs only), key_bits is
+    to_key away from NaN, from_key returns the bits of every non-NaN, and every NaN has the key KEY_NAN."""
+    fixed = [0x00000000, 0x80000000, 0x00000001, 0x80000001, 0x007FFFFF, 0x807FFFFF, 0x00800000, 0x80800000, 0x7F7FFFFF, 0xFF7FFFFF,
+             0x3F800000, 0xBF800000, 0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0x7FC12345, 0xFFC12345, 0x7F800001, 0xFF800001,
+             0x7FA54321, 0xFFA54321, 0x7FFFFFFF, 0xFFFFFFFF]
+    bits = np.concatenate([np.array(fixed, dtype=np.uint32),
+                           np.random.default_rng(21).integers(0, 1 << 32, 4096, dtype=np.uint64).astype(np.uint32)])
+    path = tmp_path / "bits.txt"
+    path.write_text("\n".join(f"{int(b):08x}" for b in bits) + "\n")
+    r = subprocess.run([network_program, "keys", str(path)], capture_output=True, text=True, check=True)
+    rows = np.array([[int(v, 16) for v in line.split()] for line in r.stdout.splitlines()], dtype=np.uint64)
+    assert rows.shape == (bits.size, 4) and np.array_equal(rows[:, 0], bits)
+    key, raw, back = rows[:, 1], rows[:, 2], rows[:, 3]
+    x = bits.view(np.float32)
+    nan = np.isnan(x)
+    assert nan.sum() >= 10 and (~nan).sum() >= 4000
+    assert np.all(key[nan] == 0xFFC00000) and np.all(key[~nan] < 0xFFC00000)
+    assert np.array_equal(raw[~nan], key[~nan]) and np.array_equal(back[~nan], bits[~nan])
+    by_key = x[np.argsort(key, kind="stable")]
+    assert np.array_equal(by_key, np.sort(x), equal_nan=True)
+    # ties between NaNs only: different bits have different keys, -0 below +0
+    ub, first = np.unique(bits[~nan], return_index=True)
+    assert np.unique(key[~nan][first]).size == ub.size and key[1] < key[0]
 
 
 # ------------------------------------------------------------------------------------------------ interface
