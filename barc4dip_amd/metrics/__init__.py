@@ -11,7 +11,9 @@ from .multitau import multi_tau_correlation
 from . import order
 from .order import temporal_median, temporal_percentile, temporal_robust_mean
 from .twotime import correlation_decay, two_time_correlation
+from . import contrast
+from .contrast import local_contrast
 
 __all__ = ["order", "temporal_median", "temporal_percentile", "temporal_robust_mean","sharpness", "sharpness_stats", "sharpness_stack_stats", "statistics", "speckles", "speckle_stats",
            "speckle_stack_stats", "distribution_moments", "temporal", "temporal_stats", "sharded", "kernels", "twotime",
-           "two_time_correlation", "correlation_decay", "multitau", "multi_tau_correlation"]
+           "two_time_correlation", "correlation_decay", "multitau", "multi_tau_correlation", "contrast", "local_contrast"]

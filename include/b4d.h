@@ -771,6 +771,38 @@ int b4d_temporal_robust_mean(const float* stack, int T, long long frame_stride, 
                              float min_scale, int polarity, int flags, float* mean, float* median, float* scale, unsigned short* n_kept,
                              unsigned char* rejected, float* cleaned, long long out_stride, void* stream);
 
+/* Linear separable filters and local statistics on every frame of (batch, ny, nx) float32 (barc4dip_amd.preprocessing.smooth,
+ * barc4dip_amd.metrics.contrast).  Frames and outputs are DEVICE pointers, the taps HOST float64 arrays
+ * that are read before the call returns (they travel in the kernel arguments); asynchronous on `stream`, no synchronisation.
+ * mode and cval: the codes and meanings of b4d_rank_filter (0 nearest, 1 reflect, 2 mirror, 3 constant, 4 wrap), for any overhang.
+ * b4d_separable_filter: a correlation with SciPy's placement (scipy.ndimage.correlate1d, origin 0) along x, then along y:
+ *     r[y, x] = sum_k wx[k] in[y, x - n_x / 2 + k]        g[y, x] = sum_k wy[k] r[y - n_y / 2 + k, x]
+ *   (integer division: an even window is one sample longer on the left).  The border rule of the second pass sees r, as SciPy's
+ *   sequence of 1-D filters does: under "constant" a row of r outside the frame is cval.  Each tap is rounded once to float32; a
+ *   sum starts with its first product and adds the others by float32 FMA in ascending k, on both routes, which therefore give
+ *   the same bits.  An axis with n = 1 and w = {1} is skipped.  Non-finite input propagates as IEEE arithmetic does: a NaN
+ *   poisons exactly the outputs whose windows contain it, taps that are zero included.
+ *   epilogue, applied in the last pass to g and the input pixel x: 0 out = g; 1 out = x - g; 2 out = x / max(g, eps) (max as
+ *   np.maximum: a NaN g stays).  1 <= n <= 511 per axis.
+ *   flags bit 0: take the two-pass route (row kernel -> the library's per-stream scratch buffer, at most 128 MiB of it -> column
+ *   kernel) also where the fused route (one launch, both passes in LDS) applies: half-widths up to 4, i.e. n <= 9 per axis.
+ *   flags bit 1: take the fused route up to n <= 49 per axis (what its kernel can hold; for timing the boundary).
+ *   16-byte accesses to memory where nx % 4 == 0 and the base is 16-byte aligned, dword accesses otherwise; the same bits.
+ * b4d_local_stats: windowed mean, population variance and contrast of the size_y x size_x window (1 .. 63 per axis, SciPy's
+ *   placement) of the frame padded in two dimensions by the border rule.  taps_y = taps_x = NULL: box window, S1 = sum x,
+ *   S2 = sum x * x, W = size_y size_x.  Otherwise both are given (size_y and size_x float64 taps): S1 = sum wy wx x,
+ *   S2 = sum wy wx x * x, W = sum wy wx, summed by the same code.  x * x is formed in float64 (exact) and every sum is float64,
+ *   along x, then along y, in ascending tap order.  mean = S1 / W, variance = max(S2 / W - mean * mean, 0) (a NaN stays),
+ *   contrast = sqrt(variance) / mean where mean > 0, NaN elsewhere; each (batch, ny, nx) float32 or NULL.  On integer-valued
+ *   frames the box sums are exact.  One launch, one read of the stack.
+ * No atomics: a frame gives the same bits alone and inside any batch.  All argument errors are returned before any launch:
+ * B4D_EINVAL for tap counts, sizes, mode or epilogue out of range, batch < 1, a null frame or tap pointer, an output that overlaps
+ * the input (in == out), no output at all; B4D_ESIZE where ny * nx >= 2^31.                                                  */
+int b4d_separable_filter(const float* in, int batch, int ny, int nx, const double* taps_y, int n_y, const double* taps_x, int n_x,
+                         int mode, float cval, int epilogue, float eps, int flags, float* out, void* stream);
+int b4d_local_stats(const float* in, int batch, int ny, int nx, int size_y, int size_x, const double* taps_y, const double* taps_x,
+                    int mode, float cval, float* mean, float* variance, float* contrast, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
