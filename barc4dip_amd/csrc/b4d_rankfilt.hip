@@ -21,7 +21,6 @@
 namespace b4d {
 using namespace rankfilt;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 
 // register route: 128 x 32 outputs per workgroup, 32 lanes x 4 outputs across, 8 lane rows x 4 passes down; the halo in x is padded
@@ -159,17 +158,9 @@ __global__ void __launch_bounds__(256) k_median_reg(const float* __restrict__ in
             uint32_t w[S][12], med[4];
             load_window<S>(lds, ly, tx, w);
             medians4<S>(w, med);
-            if (out) {
-                float* o = out + fo + (size_t)(y0 + ly) * nx + ox;
-                if (vec_out && ox + 3 < nx) {
-                    __builtin_nontemporal_store(v4f{from_key(med[0]), from_key(med[1]), from_key(med[2]), from_key(med[3])},
-                                                reinterpret_cast<v4f*>(o));
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (ox + c < nx) o[c] = from_key(med[c]);
-                }
-            }
+            if (out)
+                store4(out + fo + (size_t)(y0 + ly) * nx + ox, v4f{from_key(med[0]), from_key(med[1]), from_key(med[2]), from_key(med[3])}, nx - ox,
+                       vec_out != 0, true);
             if (mm) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
@@ -285,22 +276,8 @@ __global__ void __launch_bounds__(256) k_despeckle(const float* __restrict__ in,
                 if (ox + c < nx) cnt += flag[c];
             }
             const size_t po = fo + (size_t)(y0 + ly) * nx + ox;
-            if (vec_out && ox + 3 < nx) {
-                __builtin_nontemporal_store(v4f{res[0], res[1], res[2], res[3]}, reinterpret_cast<v4f*>(out + po));
-            } else {
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    if (ox + c < nx) out[po + c] = res[c];
-            }
-            if (mask) {
-                if (vec_mask && ox + 3 < nx) {
-                    *reinterpret_cast<uint32_t*>(mask + po) = (uint32_t)flag[0] | ((uint32_t)flag[1] << 8) | ((uint32_t)flag[2] << 16) | ((uint32_t)flag[3] << 24);
-                } else {
-#pragma unroll
-                    for (int c = 0; c < 4; ++c)
-                        if (ox + c < nx) mask[po + c] = flag[c];
-                }
-            }
+            store4(out + po, v4f{res[0], res[1], res[2], res[3]}, nx - ox, vec_out != 0, true);
+            if (mask) store4(mask + po, flag, nx - ox, vec_mask != 0);
         }
     }
     if (counts) {
@@ -340,19 +317,19 @@ __global__ void __launch_bounds__(256) k_scale_u16_vec(const float* __restrict__
     }
 }
 
-constexpr int MAX_GRID_Z = 65535;
-
-template <int S>
-static void launch_median_reg(const float* in, int frames, int ny, int nx, int mode, float cval, float* out, uint32_t* mm, int vec_in,
-                              int vec_out, hipStream_t st) {
-    hipLaunchKernelGGL(k_median_reg<S>, dim3((nx + RF_TX - 1) / RF_TX, (ny + RF_TY - 1) / RF_TY, frames), dim3(256), 0, st, in, ny, nx, mode, cval,
-                       out, mm, vec_in, vec_out);
+static dim3 rf_grid(int ny, int nx, int frames) { return dim3((nx + RF_TX - 1) / RF_TX, (ny + RF_TY - 1) / RF_TY, frames); }
+// the register-route kernel of window size 3, 5 or 7
+template <class... A>
+static int launch_median_reg(int size, dim3 grid, hipStream_t st, const A&... args) {
+    if (size == 3) return launch(k_median_reg<3>, grid, dim3(256), 0, st, args...);
+    if (size == 5) return launch(k_median_reg<5>, grid, dim3(256), 0, st, args...);
+    return launch(k_median_reg<7>, grid, dim3(256), 0, st, args...);
 }
-template <int S>
-static void launch_despeckle(const float* in, int frames, int ny, int nx, int mode, float cval, float* out, unsigned char* mask,
-                             unsigned long long* counts, OutlierRule a, int vec_in, int vec_out, int vec_mask, hipStream_t st) {
-    hipLaunchKernelGGL(k_despeckle<S>, dim3((nx + RF_TX - 1) / RF_TX, (ny + RF_TY - 1) / RF_TY, frames), dim3(256), 0, st, in, ny, nx, mode, cval,
-                       out, mask, counts, a, vec_in, vec_out, vec_mask);
+template <class... A>
+static int launch_despeckle(int size, dim3 grid, hipStream_t st, const A&... args) {
+    if (size == 3) return launch(k_despeckle<3>, grid, dim3(256), 0, st, args...);
+    if (size == 5) return launch(k_despeckle<5>, grid, dim3(256), 0, st, args...);
+    return launch(k_despeckle<7>, grid, dim3(256), 0, st, args...);
 }
 
 }  // namespace b4d
@@ -361,10 +338,9 @@ using namespace b4d;
 
 extern "C" int b4d_rank_filter(const float* in, int batch, int ny, int nx, int size_y, int size_x, int rank, int mode, float cval, int flags,
                                float* out, float* minmax, void* stream) {
-    if (!in || batch < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "b4d_rank_filter: null input or empty shape");
+    if (const int rc = check_stack("b4d_rank_filter", "null input or empty shape", in, batch, ny, nx, mode, false)) return rc;
     if (size_y < 1 || size_y > 15 || size_x < 1 || size_x > 15) return fail(B4D_EINVAL, "b4d_rank_filter: window sizes must be in 1 .. 15");
     if (rank < 0 || rank >= size_y * size_x) return fail(B4D_EINVAL, "b4d_rank_filter: rank must be in [0, size_y * size_x)");
-    if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_rank_filter: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     if (!out && !minmax) return fail(B4D_EINVAL, "b4d_rank_filter: out and minmax are both null");
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
     if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(in, bytes, minmax, 8 * (size_t)batch) || ranges_overlap(out, bytes, minmax, 8 * (size_t)batch))
@@ -372,33 +348,28 @@ extern "C" int b4d_rank_filter(const float* in, int batch, int ny, int nx, int s
     if ((ny + GN_TY - 1) / GN_TY > 65535) return fail(B4D_ESIZE, "b4d_rank_filter: more than 65535 row tiles");
     hipStream_t st = (hipStream_t)stream;
     uint32_t* mm = reinterpret_cast<uint32_t*>(minmax);
-    const int vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0, vec_out = (out && nx % 4 == 0 && ptr_aligned(out, 16)) ? 1 : 0;
+    const int vec_in = vec_ok(in, nx, 16), vec_out = vec_ok(out, nx, 16);
     const bool reg = !(flags & 1) && size_y == size_x && (size_y == 3 || size_y == 5 || size_y == 7) && rank == size_y * size_x / 2;
-    if (mm) hipLaunchKernelGGL(k_range_init, dim3((batch + 255) / 256), dim3(256), 0, st, mm, batch);
-    for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Z) {
-        const int nb = std::min(MAX_GRID_Z, batch - b0);
+    if (mm)
+        if (const int rc = launch(k_range_init, dim3((batch + 255) / 256), dim3(256), 0, st, mm, batch)) return rc;
+    const int rc = for_frame_chunks(batch, MAX_GRID_FRAMES, [&](int b0, int nb) {
         const float* pin = in + fpix * b0;
         float* pout = out ? out + fpix * b0 : nullptr;
         uint32_t* pmm = mm ? mm + 2 * (size_t)b0 : nullptr;
-        if (reg && size_y == 3) launch_median_reg<3>(pin, nb, ny, nx, mode, cval, pout, pmm, vec_in, vec_out, st);
-        else if (reg && size_y == 5) launch_median_reg<5>(pin, nb, ny, nx, mode, cval, pout, pmm, vec_in, vec_out, st);
-        else if (reg) launch_median_reg<7>(pin, nb, ny, nx, mode, cval, pout, pmm, vec_in, vec_out, st);
-        else
-            hipLaunchKernelGGL(k_rank_general, dim3((nx + GN_TX - 1) / GN_TX, (ny + GN_TY - 1) / GN_TY, nb), dim3(256), 0, st, pin, ny, nx, size_y,
-                               size_x, rank, mode, cval, pout, pmm, vec_in);
-    }
-    if (mm) hipLaunchKernelGGL(k_range_final, dim3((batch + 255) / 256), dim3(256), 0, st, mm, batch);
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+        if (reg) return launch_median_reg(size_y, rf_grid(ny, nx, nb), st, pin, ny, nx, mode, cval, pout, pmm, vec_in, vec_out);
+        return launch(k_rank_general, dim3((nx + GN_TX - 1) / GN_TX, (ny + GN_TY - 1) / GN_TY, nb), dim3(256), 0, st, pin, ny, nx, size_y, size_x, rank,
+                      mode, cval, pout, pmm, vec_in);
+    });
+    if (rc || !mm) return rc;
+    return launch(k_range_final, dim3((batch + 255) / 256), dim3(256), 0, st, mm, batch);
 }
 
 extern "C" int b4d_despeckle(const float* in, int batch, int ny, int nx, int size, int scale_kind, float threshold, float min_scale, int polarity,
                              int mode, float cval, float* out, unsigned char* mask, long long* counts, void* stream) {
-    if (!in || !out || batch < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "b4d_despeckle: null frames or empty shape");
+    if (const int rc = check_stack("b4d_despeckle", "null frames or empty shape", in && out, batch, ny, nx, mode, false)) return rc;
     if (size != 3 && size != 5 && size != 7) return fail(B4D_EINVAL, "b4d_despeckle: size must be 3, 5 or 7");
     if (scale_kind < 0 || scale_kind > 2 || polarity < 0 || polarity > 2) return fail(B4D_EINVAL, "b4d_despeckle: scale_kind / polarity must be 0, 1 or 2");
     if (!(threshold >= 0.f) || !(min_scale >= 0.f)) return fail(B4D_EINVAL, "b4d_despeckle: threshold and min_scale must be >= 0");
-    if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_despeckle: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     const size_t fpix = (size_t)ny * nx, npix = fpix * batch, bytes = npix * sizeof(float);
     if (ranges_overlap(in, bytes, out, bytes) || ranges_overlap(in, bytes, mask, npix) || ranges_overlap(out, bytes, mask, npix) ||
         ranges_overlap(in, bytes, counts, 8 * (size_t)batch) || ranges_overlap(out, bytes, counts, 8 * (size_t)batch))
@@ -406,22 +377,13 @@ extern "C" int b4d_despeckle(const float* in, int batch, int ny, int nx, int siz
     if ((ny + RF_TY - 1) / RF_TY > 65535) return fail(B4D_ESIZE, "b4d_despeckle: more than 65535 row tiles");
     hipStream_t st = (hipStream_t)stream;
     const OutlierRule a = make_outlier_rule(scale_kind, threshold, min_scale, polarity);
-    const int vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0, vec_out = (nx % 4 == 0 && ptr_aligned(out, 16)) ? 1 : 0;
-    const int vec_mask = (mask && nx % 4 == 0 && ptr_aligned(mask, 4)) ? 1 : 0;
+    const int vec_in = vec_ok(in, nx, 16), vec_out = vec_ok(out, nx, 16), vec_mask = vec_ok(mask, nx, 4);
     unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
     if (cnt) B4D_HIP(hipMemsetAsync(cnt, 0, 8 * (size_t)batch, st));
-    for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Z) {
-        const int nb = std::min(MAX_GRID_Z, batch - b0);
-        const float* pin = in + fpix * b0;
-        float* pout = out + fpix * b0;
-        unsigned char* pmask = mask ? mask + fpix * b0 : nullptr;
-        unsigned long long* pcnt = cnt ? cnt + b0 : nullptr;
-        if (size == 3) launch_despeckle<3>(pin, nb, ny, nx, mode, cval, pout, pmask, pcnt, a, vec_in, vec_out, vec_mask, st);
-        else if (size == 5) launch_despeckle<5>(pin, nb, ny, nx, mode, cval, pout, pmask, pcnt, a, vec_in, vec_out, vec_mask, st);
-        else launch_despeckle<7>(pin, nb, ny, nx, mode, cval, pout, pmask, pcnt, a, vec_in, vec_out, vec_mask, st);
-    }
-    B4D_HIP(hipGetLastError());
-    return B4D_OK;
+    return for_frame_chunks(batch, MAX_GRID_FRAMES, [&](int b0, int nb) {
+        return launch_despeckle(size, rf_grid(ny, nx, nb), st, in + fpix * b0, ny, nx, mode, cval, out + fpix * b0, mask ? mask + fpix * b0 : nullptr,
+                                cnt ? cnt + b0 : nullptr, a, vec_in, vec_out, vec_mask);
+    });
 }
 
 extern "C" int b4d_scale_to_u16(const float* in, size_t n, float vmin, double inv, int mul_f64, unsigned short* out, void* stream) {
@@ -431,13 +393,12 @@ extern "C" int b4d_scale_to_u16(const float* in, size_t n, float vmin, double in
     size_t done = 0;
     if (ptr_aligned(in, 16) && ptr_aligned(out, 8) && n >= 4) {
         const size_t nvec = n / 4;
-        hipLaunchKernelGGL(k_scale_u16_vec, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 65535)), dim3(256), 0, st, in, nvec, vmin, inv, mul_f64,
-                           out);
+        if (const int rc = launch(k_scale_u16_vec, dim3((unsigned)std::min<size_t>((nvec + 255) / 256, 65535)), dim3(256), 0, st, in, nvec, vmin, inv, mul_f64, out))
+            return rc;
         done = nvec * 4;
     }
     if (done < n)
-        hipLaunchKernelGGL(k_scale_u16, dim3((unsigned)std::min<size_t>((n - done + 255) / 256, 65535)), dim3(256), 0, st, in + done, n - done, vmin,
-                           inv, mul_f64, out + done);
-    B4D_HIP(hipGetLastError());
+        return launch(k_scale_u16, dim3((unsigned)std::min<size_t>((n - done + 255) / 256, 65535)), dim3(256), 0, st, in + done, n - done, vmin, inv, mul_f64,
+                      out + done);
     return B4D_OK;
 }

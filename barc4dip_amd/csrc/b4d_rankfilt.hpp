@@ -1,8 +1,9 @@
-// b4d_rankfilt.hpp -- what is spatial in the rank filters (b4d_rankfilt.hip): the selection networks of the 3 x 3 .. 7 x 7 windows
-// and the border rule.  The keys, the operations policy O and cex come from b4d_keys.hpp.  Everything here is __host__ __device__
+// b4d_rankfilt.hpp -- what is spatial in the rank filters (b4d_rankfilt.hip): the selection networks of the 3 x 3 .. 7 x 7
+// windows.  The border rule comes from b4d_tile.hpp; the keys, the operations policy O and cex come from b4d_keys.hpp.  Everything here is __host__ __device__
 // and free of HIP types, so a plain C++ program can include it and test the networks (tests/test_rank_filter_host.py).
 #pragma once
 #include "b4d_keys.hpp"
+#include "b4d_tile.hpp"
 
 namespace b4d {
 namespace rankfilt {   // (sees namespace keys: b4d_keys.hpp)
@@ -107,23 +108,7 @@ B4D_HD typename O::T median_sorted_cols(const typename O::T (&col)[S][S]) {
     return median_forgetful<O, K>(keep);
 }
 
-// source index of position i on an axis of n samples under scipy.ndimage's border modes, for any overhang (repeated
-// reflection / wrap); -1 = outside (mode "constant").  Codes as in b4d_warp_*: 0 nearest, 1 reflect, 2 mirror, 3 constant; 4 wrap.
-enum { MODE_NEAREST = 0, MODE_REFLECT = 1, MODE_MIRROR = 2, MODE_CONSTANT = 3, MODE_WRAP = 4 };
-B4D_HD int border_index(int i, int n, int mode) {
-    if (i >= 0 && i < n) return i;
-    if (mode == MODE_CONSTANT) return -1;
-    if (mode == MODE_NEAREST || n == 1) return i < 0 ? 0 : n - 1;
-    if (mode == MODE_WRAP) {
-        i %= n;
-        return i < 0 ? i + n : i;
-    }
-    const int p = mode == MODE_REFLECT ? 2 * n : 2 * n - 2;   // reflect: d c b a | a b c d | d c b a; mirror: d c b | a b c d | c b a
-    i %= p;
-    if (i < 0) i += p;
-    if (i < n) return i;
-    return mode == MODE_REFLECT ? p - 1 - i : p - i;
-}
+using b4d::border_index;   // the border rule (b4d_tile.hpp), under the name it had here
 
 }  // namespace rankfilt
 }  // namespace b4d

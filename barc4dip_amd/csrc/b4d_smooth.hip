@@ -18,12 +18,10 @@
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
-#include "b4d_rankfilt.hpp"
+#include "b4d_tile.hpp"
 
 namespace b4d {
-using rankfilt::border_index;
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 
 constexpr int SM_MAX_TAPS = 511;
@@ -41,7 +39,6 @@ constexpr int SC_TX = 32, SC_TY = 256, SC_PITCH = SC_TX + 4;
 constexpr int SF_T = 64, SF_PITCH_B = SF_T + 4;
 // local statistics: 32 x 32 outputs per workgroup, windows up to 63 x 63
 constexpr int LS_T = 32, LS_MAX = 63;
-constexpr int MAX_GRID_Y = 65535;
 
 struct Taps {   // one axis, float32, zero beyond n (never multiplied: 0 * NaN would widen a NaN's footprint)
     int n;
@@ -97,19 +94,18 @@ __device__ __forceinline__ void stage(float* __restrict__ lds, int pitch, const 
                                       int ncols, int mode, float cval, bool vec) {
     const int xa = xs & ~3;
     const int ng = (xs + ncols - xa + 3) >> 2;
-    const int dq = 256 / ng, dr = 256 - dq * ng;
-    int j = threadIdx.x / ng, g = threadIdx.x - j * ng;
-    while (j < nrows) {
+    TileWalk w = tile_walk(threadIdx.x, ng);
+    while (w.j < nrows) {
         v4f q[4];
         int at[4], c0[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             at[u] = -1;
             q[u] = v4f{cval, cval, cval, cval};
-            if (j < nrows) {
-                const int yy = border_index(ys + j, ny, mode);
-                const int xb = xa + 4 * g;
-                at[u] = j;
+            if (w.j < nrows) {
+                const int yy = border_index(ys + w.j, ny, mode);
+                const int xb = xa + 4 * w.g;
+                at[u] = w.j;
                 c0[u] = xb - xs;
                 if (yy >= 0) {
                     const float* row = f + (size_t)yy * nx;
@@ -124,12 +120,7 @@ __device__ __forceinline__ void stage(float* __restrict__ lds, int pitch, const 
                     }
                 }
             }
-            g += dr;
-            j += dq;
-            if (g >= ng) {
-                g -= ng;
-                ++j;
-            }
+            tile_step(w);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -230,18 +221,6 @@ __device__ __forceinline__ float epilogue(int epi, float g, float x, float eps) 
     return g;
 }
 
-// four values to out[0 .. 4) of a row that ends `left` elements from out; 16 bytes where vec (final: streaming store)
-__device__ __forceinline__ void store4(float* __restrict__ out, v4f v, int left, bool vec, bool final) {
-    if (vec && left >= 4) {
-        if (final) __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(out));
-        else *reinterpret_cast<v4f*>(out) = v;
-    } else {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-            if (e < left) out[e] = v[e];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- two-pass route
 // grid (tiles_x * tiles_y, frames); dynamic LDS SR_TY / 2 row pairs of pitch pair_width(SR_TX + up8(n)).  A lane filters 8 outputs of
 // two rows.  epi is applied when this is the only pass (-1: this is the first of two: plain stores, the intermediate is read again).
@@ -336,7 +315,7 @@ __global__ void __launch_bounds__(256) k_smooth_fused(Frame a, TapsFused t) {
         const float* row = A + r * pitch_a;
         float acc[8];
         const int yy = y0 - loy + r;
-        if (a.mode == rankfilt::MODE_CONSTANT && (yy < 0 || yy >= a.ny)) {
+        if (a.mode == MODE_CONSTANT && (yy < 0 || yy >= a.ny)) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) acc[j] = a.cval;
         } else if (id_x) {
@@ -463,12 +442,10 @@ using namespace b4d;
 extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, const double* taps_y, int n_y, const double* taps_x, int n_x,
                                     int mode, float cval, int epilogue, float eps, int flags, float* out, void* stream) {
     if (!in || !out || !taps_y || !taps_x) return fail(B4D_EINVAL, "b4d_separable_filter: null argument");
-    if (batch < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "b4d_separable_filter: empty shape");
+    if (const int rc = check_stack("b4d_separable_filter", "empty shape", true, batch, ny, nx, mode, true)) return rc;
     if (n_y < 1 || n_y > SM_MAX_TAPS || n_x < 1 || n_x > SM_MAX_TAPS)
         return fail(B4D_EINVAL, "b4d_separable_filter: tap counts must be in 1 .. " + std::to_string(SM_MAX_TAPS));
-    if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_separable_filter: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     if (epilogue < 0 || epilogue > 2) return fail(B4D_EINVAL, "b4d_separable_filter: epilogue must be 0 filtered, 1 subtract or 2 divide");
-    if ((long long)ny * nx >= (1LL << 31)) return fail(B4D_ESIZE, "b4d_separable_filter: 2^31 or more pixels per frame");
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
     if (ranges_overlap(in, bytes, out, bytes)) return fail(B4D_EINVAL, "b4d_separable_filter: in and out must not overlap");
     hipStream_t st = (hipStream_t)stream;
@@ -478,7 +455,7 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
     a.mode = mode;
     a.cval = cval;
     a.eps = eps;
-    const int vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0, vec_out = (nx % 4 == 0 && ptr_aligned(out, 16)) ? 1 : 0;
+    const int vec_in = vec_ok(in, nx, 16), vec_out = vec_ok(out, nx, 16);
     const bool id_y = n_y == 1 && (float)taps_y[0] == 1.f, id_x = n_x == 1 && (float)taps_x[0] == 1.f;
     const int fused_max = (flags & 2) ? SM_FUSED_CAP : SM_FUSED_TAPS;
     const bool fused = !(flags & 1) && n_y <= fused_max && n_x <= fused_max;
@@ -492,13 +469,11 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
         a.vec_in = vec_in;
         a.vec_out = vec_out;
         a.epi = epilogue;
-        for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Y) {
-            const int nb = std::min(MAX_GRID_Y, batch - b0);
+        return for_frame_chunks(batch, MAX_GRID_FRAMES, [&](int b0, int nb) {
             a.in = in + fpix * b0;
             a.out = out + fpix * b0;
-            if (const int rc = launch(k_smooth_fused, dim3(a.tiles_x * tiles(ny, SF_T), nb), dim3(256), lds_fused(n_y, n_x), st, a, t)) return rc;
-        }
-        return B4D_OK;
+            return launch(k_smooth_fused, dim3(a.tiles_x * tiles(ny, SF_T), nb), dim3(256), lds_fused(n_y, n_x), st, a, t);
+        });
     }
     // two passes, a group of frames at a time so that the intermediate of a group stays in the last-level cache; an identity axis
     // is skipped (with both, the row kernel copies with its one tap)
@@ -508,7 +483,7 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
     round_taps(taps_x, n_x, tx.w, SM_MAX_TAPS + 1);
     round_taps(taps_y, n_y, ty.w, SM_MAX_TAPS + 1);
     const bool do_col = !id_y, do_row = !id_x || !do_col;
-    const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)MAX_GRID_Y, ((size_t)128 << 20) / (fpix * sizeof(float))));
+    const int group = (int)std::max<size_t>(1, std::min<size_t>((size_t)MAX_GRID_FRAMES, ((size_t)128 << 20) / (fpix * sizeof(float))));
     B4D_SCRATCH_LOCK();
     float* mid = nullptr;
     if (do_row && do_col) {
@@ -516,8 +491,7 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
         if (const int rc = get_scratch(fpix * std::min(group, batch) * sizeof(float), &p, st)) return rc;
         mid = static_cast<float*>(p);
     }
-    for (int b0 = 0; b0 < batch; b0 += group) {
-        const int nb = std::min(group, batch - b0);
+    return for_frame_chunks(batch, group, [&](int b0, int nb) {
         const float* pin = in + fpix * b0;
         float* pout = out + fpix * b0;
         if (do_row) {
@@ -538,19 +512,17 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
             a.epi = epilogue;
             if (const int rc = launch(k_smooth_col, dim3(a.tiles_x * tiles(ny, SC_TY), nb), dim3(256), lds_col(n_y), st, a, pin, vec_in, ty)) return rc;
         }
-    }
-    return B4D_OK;
+        return B4D_OK;
+    });
 }
 
 extern "C" int b4d_local_stats(const float* in, int batch, int ny, int nx, int size_y, int size_x, const double* taps_y, const double* taps_x,
                                int mode, float cval, float* mean, float* variance, float* contrast, void* stream) {
-    if (!in || batch < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "b4d_local_stats: null input or empty shape");
+    if (const int rc = check_stack("b4d_local_stats", "null input or empty shape", in, batch, ny, nx, mode, true)) return rc;
     if (size_y < 1 || size_y > LS_MAX || size_x < 1 || size_x > LS_MAX)
         return fail(B4D_EINVAL, "b4d_local_stats: window sizes must be in 1 .. " + std::to_string(LS_MAX));
     if ((taps_y == nullptr) != (taps_x == nullptr)) return fail(B4D_EINVAL, "b4d_local_stats: taps_y and taps_x must both be given or both be null");
-    if (mode < 0 || mode > 4) return fail(B4D_EINVAL, "b4d_local_stats: mode must be 0 nearest, 1 reflect, 2 mirror, 3 constant or 4 wrap");
     if (!mean && !variance && !contrast) return fail(B4D_EINVAL, "b4d_local_stats: mean, variance and contrast are all null");
-    if ((long long)ny * nx >= (1LL << 31)) return fail(B4D_ESIZE, "b4d_local_stats: 2^31 or more pixels per frame");
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
     if (ranges_overlap(in, bytes, mean, bytes) || ranges_overlap(in, bytes, variance, bytes) || ranges_overlap(in, bytes, contrast, bytes))
         return fail(B4D_EINVAL, "b4d_local_stats: an output overlaps the input");
@@ -567,14 +539,11 @@ extern "C" int b4d_local_stats(const float* in, int batch, int ny, int nx, int s
     a.mode = mode;
     a.cval = cval;
     a.tiles_x = (int)tiles(nx, LS_T);
-    a.vec_in = (nx % 4 == 0 && ptr_aligned(in, 16)) ? 1 : 0;
-    for (int b0 = 0; b0 < batch; b0 += MAX_GRID_Y) {
-        const int nb = std::min(MAX_GRID_Y, batch - b0);
+    a.vec_in = vec_ok(in, nx, 16);
+    return for_frame_chunks(batch, MAX_GRID_FRAMES, [&](int b0, int nb) {
         a.in = in + fpix * b0;
         a.out = mean ? mean + fpix * b0 : nullptr;
-        if (const int rc = launch(k_local_stats, dim3(a.tiles_x * tiles(ny, LS_T), nb), dim3(256), lds_stats(size_y, size_x), st, a,
-                                  variance ? variance + fpix * b0 : nullptr, contrast ? contrast + fpix * b0 : nullptr, t))
-            return rc;
-    }
-    return B4D_OK;
+        return launch(k_local_stats, dim3(a.tiles_x * tiles(ny, LS_T), nb), dim3(256), lds_stats(size_y, size_x), st, a,
+                      variance ? variance + fpix * b0 : nullptr, contrast ? contrast + fpix * b0 : nullptr, t);
+    });
 }

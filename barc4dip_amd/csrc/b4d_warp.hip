@@ -17,10 +17,10 @@
 #include <string>
 
 #include "b4d_common.hpp"
+#include "b4d_tile.hpp"   // MODE_*
 
 namespace b4d {
 
-enum { WM_NEAREST = 0, WM_REFLECT = 1, WM_MIRROR = 2, WM_CONSTANT = 3 };
 constexpr int WP_PAD = 12;          // "nearest", order 3: edge padding of the frame before the prefilter (scipy's npad)
 constexpr int WP_R = 14;            // FIR half-length: |sqrt(3) - 2|^15 = 2.7e-9
 constexpr int WP_RB = 8;            // output rows per lane of the column pass
@@ -42,11 +42,12 @@ struct FirTaps {
 constexpr FirTaps kFir{};
 
 // index i of a signal of n samples folded back into [0, n): edge clamp, half-sample ("reflect": -1 -> 0) or whole-sample
-// ("mirror": -1 -> 1) symmetric extension
+// ("mirror": -1 -> 1) symmetric extension.  border_index (b4d_tile.hpp) gives the same indices for these three modes; with its
+// branches for "constant" and "wrap" k_prefilter_row takes 66 VGPRs instead of 37 and loses a wave per SIMD, so the fold stays.
 __device__ __forceinline__ int wp_fold(int i, int n, int mode) {
     if ((unsigned)i < (unsigned)n) return i;
-    if (mode == WM_NEAREST) return i < 0 ? 0 : n - 1;
-    if (mode == WM_REFLECT) {
+    if (mode == MODE_NEAREST) return i < 0 ? 0 : n - 1;
+    if (mode == MODE_REFLECT) {
         const int p = 2 * n;
         i %= p;
         if (i < 0) i += p;
@@ -61,8 +62,8 @@ __device__ __forceinline__ int wp_fold(int i, int n, int mode) {
 
 // extension used by the prefilter (fm) and by the taps (tm) of a mode; "constant" takes the mirror route inside the frame,
 // "nearest" filters its padded frame with mirror extension and clamps the taps
-__device__ __forceinline__ int wp_filter_mode(int mode) { return mode == WM_REFLECT ? WM_REFLECT : WM_MIRROR; }
-__device__ __forceinline__ int wp_tap_mode(int mode) { return mode == WM_CONSTANT ? WM_MIRROR : mode; }
+__device__ __forceinline__ int wp_filter_mode(int mode) { return mode == MODE_REFLECT ? MODE_REFLECT : MODE_MIRROR; }
+__device__ __forceinline__ int wp_tap_mode(int mode) { return mode == MODE_CONSTANT ? MODE_MIRROR : mode; }
 
 // ---- prefilter, pass 1: src (n, h, w) -> coef (n, hp, wp) filtered along y; padded row / column i reads src row clamp(i - pad)
 __global__ void __launch_bounds__(WP_THREADS) k_prefilter_col(const float* __restrict__ src, int h, int w, int pad, int mode,
@@ -145,7 +146,7 @@ __device__ __forceinline__ void wp_cubic(float t, float (&wt)[4]) {
 
 template <int ORDER>
 __device__ __forceinline__ float wp_sample(const float* __restrict__ P, const WarpArgs& a, int y, int x, float dy, float dx) {
-    if (a.mode == WM_CONSTANT && (dy < (float)-y || dy > (float)(a.h - 1 - y) || dx < (float)-x || dx > (float)(a.w - 1 - x)))
+    if (a.mode == MODE_CONSTANT && (dy < (float)-y || dy > (float)(a.h - 1 - y) || dx < (float)-x || dx > (float)(a.w - 1 - x)))
         return a.cval;
     const int tm = wp_tap_mode(a.mode);
     float ty, tx;
@@ -249,7 +250,7 @@ static int warp_check(const float* src, int n, int h, int w, int order, int mode
     if (!src || !dy || !dx || !out) return fail(B4D_EINVAL, "null argument");
     if (n < 1 || h < 1 || w < 1) return fail(B4D_EINVAL, "frame count and sides must be >= 1");
     if (order != 0 && order != 1 && order != 3) return fail(B4D_EINVAL, "order must be 0, 1 or 3");
-    if (mode < WM_NEAREST || mode > WM_CONSTANT) return fail(B4D_EINVAL, "mode must be 0 (nearest) .. 3 (constant)");
+    if (mode < MODE_NEAREST || mode > MODE_CONSTANT) return fail(B4D_EINVAL, "mode must be 0 (nearest) .. 3 (constant)");
     if (field_frames != 1 && field_frames != n) return fail(B4D_EINVAL, "field_frames must be 1 or the frame count");
     if (n > 65535 || h > 4 * 65535 || w > WP_MAX_FOLD) return fail(B4D_ESIZE, "warp: at most 65535 frames and 262140 rows");
     return B4D_OK;
@@ -265,7 +266,7 @@ static WarpArgs warp_args(const float* src, int h, int w, int order, int mode, f
     a.fstride = field_frames == 1 ? 0 : plane;
     a.h = h;
     a.w = w;
-    a.pad = (order == 3 && mode == WM_NEAREST) ? WP_PAD : 0;
+    a.pad = (order == 3 && mode == MODE_NEAREST) ? WP_PAD : 0;
     a.sh = h + 2 * a.pad;
     a.sw = w + 2 * a.pad;
     a.mode = mode;
@@ -280,8 +281,8 @@ using namespace b4d;
 extern "C" int b4d_spline_prefilter(const float* src, int n, int h, int w, int mode, float* coef, void* stream) {
     if (!src || !coef) return fail(B4D_EINVAL, "null argument");
     if (n < 1 || h < 1 || w < 1) return fail(B4D_EINVAL, "frame count and sides must be >= 1");
-    if (mode < WM_NEAREST || mode > WM_CONSTANT) return fail(B4D_EINVAL, "mode must be 0 (nearest) .. 3 (constant)");
-    const int pad = mode == WM_NEAREST ? WP_PAD : 0, hp = h + 2 * pad, wp = w + 2 * pad;
+    if (mode < MODE_NEAREST || mode > MODE_CONSTANT) return fail(B4D_EINVAL, "mode must be 0 (nearest) .. 3 (constant)");
+    const int pad = mode == MODE_NEAREST ? WP_PAD : 0, hp = h + 2 * pad, wp = w + 2 * pad;
     if (n > 65535 || wp > WP_MAX_ROW || h > 4 * 65535)
         return fail(B4D_ESIZE, "spline prefilter: at most 65535 frames, 262140 rows and " + std::to_string(WP_MAX_ROW) +
                                    " padded columns");

@@ -6,6 +6,8 @@ import ctypes as C
 
 from .. import _device as D
 from .. import _ffi
+from .._frames import frame_stack, mode_code, pair, window as size_pair
+from ..preprocessing.smooth import gaussian_taps
 
 MAX_SIZE = 63
 MAX_HALF_WIDTH = 31
@@ -32,29 +34,19 @@ def local_contrast(images, size=7, *, window: str = "box", sigma=None, truncate:
     ``window="box"``: a ``size`` (int or pair ``(y, x)``, 1 .. 63) window of equal weights, placed as SciPy places it.
     ``window="gaussian"``: weights of ``sigma`` (scalar or pair), half-width ``int(truncate * sigma + 0.5)`` <= 31; ``size`` is
     ignored.  A NaN poisons the outputs of every window that contains it."""
-    # (imported here: preprocessing.rank itself imports from this package)
-    from ..preprocessing.rank import _frames, _mode
-    from ..preprocessing.smooth import _check_frames, _pair, gaussian_taps
-
     if window not in ("box", "gaussian"):
         raise ValueError(f"window must be 'box' or 'gaussian'; got {window!r}")
-    m = _mode(mode)
+    m = mode_code(mode)
     if window == "box":
-        try:
-            sy, sx = _pair(size, "size", int)
-        except ValueError:
-            raise ValueError(f"size must be an int or a pair (size_y, size_x) of ints; got {size!r}") from None
-        if not (1 <= sy <= MAX_SIZE and 1 <= sx <= MAX_SIZE):
-            raise ValueError(f"window sizes must be in 1 .. {MAX_SIZE}; got {(sy, sx)}")
+        sy, sx = size_pair(size, MAX_SIZE)
         wy = wx = None
     else:
         if sigma is None:
             raise ValueError("window='gaussian' needs sigma")
-        gy, gx = _pair(sigma, "sigma")
+        gy, gx = pair(sigma, "sigma")
         wy = gaussian_taps(gy, 0, truncate, max_half_width=MAX_HALF_WIDTH)
         wx = gaussian_taps(gx, 0, truncate, max_half_width=MAX_HALF_WIDTH)
         sy, sx = int(wy.size), int(wx.size)
-    _check_frames(images)
-    t, batch, ny, nx = _frames(images)
+    t, batch, ny, nx = frame_stack(images)
     out = run_local_stats(t, batch, ny, nx, sy, sx, wy, wx, m, cval)
     return out if return_tensors else {k: D.to_host(v) for k, v in out.items()}

@@ -15,10 +15,11 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from .._frames import mode_code
 from ..signal import displacement as _dm
 
 ORDERS = (0, 1, 3)
-MODES = {"nearest": 0, "reflect": 1, "mirror": 2, "constant": 3}
+MODES = ("nearest", "reflect", "mirror", "constant")     # no "wrap": the spline prefilter has no periodic form
 SPLINE_PAD = 12     # "nearest", order 3: edge padding before the prefilter (b4d_spline_prefilter)
 
 
@@ -26,11 +27,13 @@ def _shape(a):
     return tuple(int(s) for s in a.shape) if D.is_tensor(a) else np.shape(a)
 
 
-def _check_order_mode(order, mode):
+def _check_order_mode(order, mode) -> int:
+    """The mode's code, after both checks."""
     if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, np.integer)) or int(order) not in ORDERS:
         raise ValueError(f"order must be one of {ORDERS}, got {order!r}")
     if not isinstance(mode, str) or mode not in MODES:
-        raise ValueError(f"mode must be one of {tuple(MODES)}, got {mode!r}")
+        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    return mode_code(mode)
 
 
 def _regular_axis(v, n: int, name: str) -> tuple[float, float]:
@@ -101,7 +104,7 @@ def correct_distortion(images, field, *, order=3, mode="nearest", cval=0.0, retu
     mode: "nearest", "reflect", "mirror" or "constant" (``cval`` where a coordinate lies outside [0, side - 1]), as scipy.
     The output has the shape of ``images`` and is float32, computed in float32 -- unlike scipy, which keeps the input dtype
     (uint16 frames would be rounded to integers).  NumPy unless ``return_tensors=True``."""
-    _check_order_mode(order, mode)
+    m = _check_order_mode(order, mode)
     ims = _check_images(images)
     f = _parse_field(field, ims)
     cval = float(cval)
@@ -117,14 +120,14 @@ def correct_distortion(images, field, *, order=3, mode="nearest", cval=0.0, retu
     if order == 3:
         p = SPLINE_PAD if mode == "nearest" else 0
         src = torch.empty((n, H + 2 * p, W + 2 * p), dtype=torch.float32, device=img.device)
-        _ffi.check(lib.b4d_spline_prefilter(D.ptr(img), n, H, W, MODES[mode], D.ptr(src), st))
+        _ffi.check(lib.b4d_spline_prefilter(D.ptr(img), n, H, W, m, D.ptr(src), st))
     out = torch.empty((n, H, W), dtype=torch.float32, device=img.device)
     if f["kind"] == "dense":
-        _ffi.check(lib.b4d_warp_dense(D.ptr(src), n, H, W, int(order), MODES[mode], cval, D.ptr(fdy), D.ptr(fdx), f["frames"],
+        _ffi.check(lib.b4d_warp_dense(D.ptr(src), n, H, W, int(order), m, cval, D.ptr(fdy), D.ptr(fdx), f["frames"],
                                       D.ptr(out), st))
     else:
         gy, gx = f["plane"]
-        _ffi.check(lib.b4d_warp_grid(D.ptr(src), n, H, W, int(order), MODES[mode], cval, D.ptr(fdy), D.ptr(fdx), f["frames"],
+        _ffi.check(lib.b4d_warp_grid(D.ptr(src), n, H, W, int(order), m, cval, D.ptr(fdy), D.ptr(fdx), f["frames"],
                                      gy, gx, f["y0"], f["sy"], f["x0"], f["sx"], D.ptr(out), st))
     out = out.reshape(ims)
     return out if return_tensors else out.cpu().numpy()

@@ -16,39 +16,10 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from .._frames import frame_stack, mode_code, window
 from ..metrics.order import _robust_args      # the outlier rule's arguments: one check for the window and the stack form
 
-_MODES = {"nearest": 0, "reflect": 1, "mirror": 2, "constant": 3, "grid-constant": 3, "wrap": 4, "grid-wrap": 4}
 MAX_SIZE = 15
-
-
-def _window(size) -> tuple[int, int]:
-    """(size_y, size_x) of an int or a pair, each in 1 .. 15."""
-    try:
-        sy, sx = (size, size) if np.ndim(size) == 0 else size
-        if int(sy) != sy or int(sx) != sx:
-            raise TypeError
-        sy, sx = int(sy), int(sx)
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be an int or a pair (size_y, size_x) of ints; got {size!r}") from None
-    if not (1 <= sy <= MAX_SIZE and 1 <= sx <= MAX_SIZE):
-        raise ValueError(f"window sizes must be in 1 .. {MAX_SIZE}; got {(sy, sx)}")
-    return sy, sx
-
-
-def _mode(mode: str) -> int:
-    if mode not in _MODES:
-        raise ValueError(f"Invalid mode: {mode!r} (expected one of {sorted(_MODES)})")
-    return _MODES[mode]
-
-
-def _frames(images):
-    """float32 device tensor of `images` ((H, W) or (T, H, W)) and its (batch, ny, nx)."""
-    t, _, _ = D.to_device_f32(images, ndim=(2, 3))
-    if t.numel() == 0:
-        raise ValueError(f"images must not be empty; got shape {tuple(t.shape)}")
-    ny, nx = int(t.shape[-2]), int(t.shape[-1])
-    return t, (int(t.shape[0]) if t.ndim == 3 else 1), ny, nx
 
 
 def run_rank_filter(t, batch, ny, nx, sy, sx, rank, mode, cval, *, general=False, want_out=True, want_range=False):
@@ -63,10 +34,10 @@ def run_rank_filter(t, batch, ny, nx, sy, sx, rank, mode, cval, *, general=False
 
 
 def _filter(images, rank_of, size, mode, cval, return_tensors, general):
-    sy, sx = _window(size)      # argument errors come before the device is asked for
-    m = _mode(mode)
+    sy, sx = window(size, MAX_SIZE)      # argument errors come before the device is asked for
+    m = mode_code(mode)
     rank = rank_of(sy * sx)
-    t, batch, ny, nx = _frames(images)
+    t, batch, ny, nx = frame_stack(images)
     out, _ = run_rank_filter(t, batch, ny, nx, sy, sx, rank, m, cval, general=general)
     return out if return_tensors else D.to_host(out)
 
@@ -120,9 +91,9 @@ def remove_outliers(images, size: int = 3, *, threshold: float = 6.0, scale: str
     if np.ndim(size) != 0 or size not in (3, 5, 7):
         raise ValueError(f"size must be 3, 5 or 7; got {size!r}")
     kind, thr, floor_, pol = _robust_args(threshold, scale, polarity, min_scale)
-    m = _mode(mode)
+    m = mode_code(mode)
     torch = _ffi.require_gpu()
-    t, batch, ny, nx = _frames(images)
+    t, batch, ny, nx = frame_stack(images)
     out = torch.empty_like(t)
     mask = torch.empty(tuple(t.shape), dtype=torch.uint8, device=t.device) if return_mask else None
     count = torch.empty((batch,), dtype=torch.int64, device=t.device) if return_mask else None

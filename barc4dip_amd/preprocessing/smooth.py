@@ -22,32 +22,11 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
-from .rank import _frames, _mode
+from .._frames import frame_stack, mode_code, pair, window
 
 MAX_TAPS = 511
 MAX_HALF_WIDTH = 255
 _EPILOGUES = {"none": 0, "subtract": 1, "divide": 2}
-
-
-def _pair(value, name, kind=float):
-    """(y, x) of a scalar or a pair."""
-    try:
-        y, x = (value, value) if np.ndim(value) == 0 else value
-        if kind is int:
-            if int(y) != y or int(x) != x:
-                raise TypeError
-        return kind(y), kind(x)
-    except (TypeError, ValueError):
-        raise ValueError(f"{name} must be a scalar or a pair (y, x); got {value!r}") from None
-
-
-def _check_frames(images) -> None:
-    """(H, W) or (T, H, W) with no empty side, checked on the host before the device is asked for."""
-    shape = tuple(images.shape) if hasattr(images, "shape") else np.shape(images)
-    if len(shape) not in (2, 3):
-        raise ValueError(f"images must be (H, W) or (T, H, W); got shape {shape}")
-    if 0 in shape:
-        raise ValueError(f"images must not be empty; got shape {shape}")
 
 
 def gaussian_taps(sigma: float, order: int = 0, truncate: float = 4.0, radius=None, *, max_half_width: int = MAX_HALF_WIDTH) -> np.ndarray:
@@ -106,10 +85,9 @@ def run_separable(t, batch, ny, nx, wy, wx, mode, cval, *, epilogue=0, eps=0.0, 
 
 
 def _apply(images, wy, wx, mode, cval, return_tensors, general, fused, epilogue=0, eps=0.0):
-    m = _mode(mode)      # argument errors come before the device is asked for
+    m = mode_code(mode)      # argument errors come before the device is asked for
     cval = float(cval)
-    _check_frames(images)
-    t, batch, ny, nx = _frames(images)
+    t, batch, ny, nx = frame_stack(images)
     out = run_separable(t, batch, ny, nx, wy, wx, m, cval, epilogue=epilogue, eps=eps, general=general, wide_fused=fused)
     return out if return_tensors else D.to_host(out)
 
@@ -125,21 +103,16 @@ def gaussian_filter(images, sigma, *, order=0, mode: str = "reflect", cval: floa
                     return_tensors: bool = False, _general: bool = False, _fused: bool = False):
     """scipy.ndimage.gaussian_filter per frame.  ``sigma``, ``order`` (0, 1 or 2) and ``radius`` are scalars or pairs ``(y, x)``;
     ``sigma == 0`` on an axis leaves that axis alone.  Half-widths up to 255."""
-    sy, sx = _pair(sigma, "sigma")
-    oy, ox = _pair(order, "order", int)
-    ry, rx = (None, None) if radius is None else _pair(radius, "radius", int)
+    sy, sx = pair(sigma, "sigma")
+    oy, ox = pair(order, "order", int)
+    ry, rx = (None, None) if radius is None else pair(radius, "radius", int)
     wy, wx = gaussian_taps(sy, oy, truncate, ry), gaussian_taps(sx, ox, truncate, rx)
     return _apply(images, wy, wx, mode, cval, return_tensors, _general, _fused)
 
 
 def uniform_filter(images, size=3, *, mode: str = "reflect", cval: float = 0.0, return_tensors: bool = False, _general: bool = False, _fused: bool = False):
     """scipy.ndimage.uniform_filter per frame: the mean of a ``size_y`` x ``size_x`` window, each side in 1 .. 511."""
-    try:
-        sy, sx = _pair(size, "size", int)
-    except ValueError:
-        raise ValueError(f"size must be an int or a pair (size_y, size_x) of ints; got {size!r}") from None
-    if not (1 <= sy <= MAX_TAPS and 1 <= sx <= MAX_TAPS):
-        raise ValueError(f"window sizes must be in 1 .. {MAX_TAPS}; got {(sy, sx)}")
+    sy, sx = window(size, MAX_TAPS)
     return _apply(images, np.full(sy, 1.0 / sy), np.full(sx, 1.0 / sx), mode, cval, return_tensors, _general, _fused)
 
 
@@ -153,6 +126,6 @@ def remove_envelope(images, sigma, *, method: str = "divide", eps=None, mode: st
     eps = float(np.finfo(np.float32).tiny) if eps is None else float(eps)
     if not eps > 0.0:
         raise ValueError(f"eps must be > 0; got {eps!r}")
-    sy, sx = _pair(sigma, "sigma")
+    sy, sx = pair(sigma, "sigma")
     wy, wx = gaussian_taps(sy, 0, truncate), gaussian_taps(sx, 0, truncate)
     return _apply(images, wy, wx, mode, cval, return_tensors, _general, _fused, epilogue=_EPILOGUES[method], eps=eps)

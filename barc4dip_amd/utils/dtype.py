@@ -12,6 +12,7 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from .._frames import frame_stack
 from .range import filtered_minmax_range
 
 
@@ -48,9 +49,7 @@ def to_uint16(data: np.ndarray, *, median_size: int = 3, counts_threshold: float
         return data
     if data.ndim not in (2, 3):
         raise ValueError(f"Expected 2D or 3D array, got ndim={data.ndim}")
-    from ..preprocessing.rank import _frames
-
-    t, _, _, _ = _frames(data)
+    t, _, _, _ = frame_stack(data)
     if _nanmean(t) > counts_threshold:
         return _scale_to_u16(t, 0.0, 1.0, False)        # x - 0 and x * 1 are exact: clip and truncate
     vmin, vmax = filtered_minmax_range(t, size=median_size)

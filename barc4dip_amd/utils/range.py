@@ -10,6 +10,7 @@ import numpy as np
 
 from .. import _device as D
 from .. import _ffi
+from .._frames import MODES, frame_stack, window
 from ..preprocessing import rank as R
 
 
@@ -22,9 +23,9 @@ def _ndim(image) -> int:
 
 def _frame_ranges(t, size):
     """(batch, 2) float32 device tensor {nanmin, nanmax} of every median-filtered frame of device tensor t."""
-    sy, sx = R._window(size)
+    sy, sx = window(size, R.MAX_SIZE)
     batch = int(t.shape[0]) if t.ndim == 3 else 1
-    _, mm = R.run_rank_filter(t, batch, int(t.shape[-2]), int(t.shape[-1]), sy, sx, (sy * sx) // 2, R._MODES["reflect"], 0.0,
+    _, mm = R.run_rank_filter(t, batch, int(t.shape[-2]), int(t.shape[-1]), sy, sx, (sy * sx) // 2, MODES["reflect"], 0.0,
                               want_out=False, want_range=True)
     return mm
 
@@ -43,8 +44,8 @@ def filtered_minmax_range(image, size: int = 3) -> tuple[float, float]:
     """(vmin, vmax) of the ``size`` x ``size`` median-filtered image (H, W) or, frame by frame, stack (N, H, W): salt-and-pepper
     suppression before scaling.  One pass over the data.  ValueError when the range is empty or not finite."""
     _ndim(image)
-    R._window(size)
-    t, _, _, _ = R._frames(image)
+    window(size, R.MAX_SIZE)
+    t, _, _, _ = frame_stack(image)
     return _bounds(_frame_ranges(t, size).cpu().numpy())
 
 
@@ -53,7 +54,7 @@ def filtered_minmax_range_streaming(image, size: int = 3, *, chunk_frames: int =
     ``ingest.iter_device_chunks`` ``chunk_frames`` frames at a time, in its native dtype, while the previous chunk is filtered."""
     if _ndim(image) == 2 or D.is_tensor(image):
         return filtered_minmax_range(image, size)
-    R._window(size)
+    window(size, R.MAX_SIZE)
     if int(np.prod(image.shape)) == 0:
         raise ValueError(f"images must not be empty; got shape {tuple(image.shape)}")
     from .. import ingest

@@ -5,7 +5,9 @@ from __future__ import annotations
 
 import numpy as np
 
-MODES = {"nearest": 0, "reflect": 1, "mirror": 2, "constant": 3, "wrap": 4}
+from barc4dip_amd._frames import MODES as _CODES
+
+MODES = {m: c for m, c in _CODES.items() if not m.startswith("grid-")}     # the five modes, without SciPy's two aliases
 U = 2.0 ** -24
 
 

@@ -79,6 +79,35 @@ def test_c_frames_smaller_than_the_window(env, mode):
             assert np.array_equal(env.R.median_filter(f, size, mode=mode, cval=-2.5, _general=general), ref), (shape, size, mode, general)
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_c_halo_wider_than_one_axis_and_one_past_a_tile_edge(env, mode):
+    """The tile stager where its paths meet: one axis shorter than the halo (3 rows or 3 columns under windows up to 15 x 15), the
+    other one element past a tile edge (261 = 2 x 128 + 5 = 8 x 32 + 5: both routes' tiles; 35 rows, 132 columns), rows of 261 and
+    3 floats (element by element), and rows of 132 floats (16 bytes) on an aligned base and on a base offset by one float."""
+    rng = np.random.default_rng(27)
+    for shape in ((3, 261), (261, 3), (35, 132)):
+        f = rng.poisson(40, shape).astype(np.float32)
+        f[rng.integers(0, shape[0], 6), rng.integers(0, shape[1], 6)] = 4000.0
+        inputs = [f]
+        if shape[1] % 4 == 0:
+            buf = env.torch.empty(f.size + 1, dtype=env.torch.float32, device="cuda")
+            off = buf[1:].view(shape)
+            off.copy_(env.torch.from_numpy(f))
+            assert off.data_ptr() % 16 != 0
+            inputs.append(off)
+        refs = {size: ndi.median_filter(f, size=size, mode=mode, cval=7.0) for size in (3, 5, 7)}
+        ranks = {(15, 100): ndi.rank_filter(f, 100, size=15, mode=mode, cval=7.0), ((2, 6), 5): ndi.rank_filter(f, 5, size=(2, 6), mode=mode, cval=7.0)}
+        want, wmask, wcount = model_remove_outliers(f, 7, scale="mad", threshold=4.0, mode=mode, cval=7.0)
+        for x in inputs:
+            for size, ref in refs.items():
+                for general in (False, True):
+                    assert np.array_equal(env.R.median_filter(x, size, mode=mode, cval=7.0, _general=general), ref), (shape, size, general)
+            for (size, rank), ref in ranks.items():
+                assert np.array_equal(env.R.rank_filter(x, rank, size, mode=mode, cval=7.0), ref), (shape, size)
+            got, info = env.R.remove_outliers(x, 7, scale="mad", threshold=4.0, mode=mode, cval=7.0, return_mask=True)
+            assert same(got, want) and np.array_equal(info["mask"], wmask) and np.array_equal(info["count"], wcount), shape
+
+
 @pytest.mark.parametrize("size", [(3, 5), (4, 4), 9, 11, 15])
 def test_d_general_route_ranks_and_percentiles(env, stack, size):
     f = stack[0, :37, :83]

@@ -194,6 +194,50 @@ def test_overhang_longer_than_the_frame(mode):
         within(p.gaussian_filter(SMALL, 5.0, radius=16, mode=mode, cval=2.5, **g), ref, bound, f"overhang 16 {mode} route {g}")
 
 
+def _offset_by_one_float(x):
+    """x on the device, on a base that is one float past a 16-byte boundary."""
+    import torch
+
+    buf = torch.empty(x.size + 1, dtype=torch.float32, device="cuda")
+    t = buf[1:].view(x.shape)
+    t.copy_(torch.from_numpy(x))
+    assert t.data_ptr() % 16 != 0
+    return t
+
+
+@pytest.mark.parametrize("mode", MODES)
+def test_halo_wider_than_one_axis_and_one_past_a_tile_edge(mode):
+    """The tile stager where its paths meet: one axis of 5 samples under windows of up to 511 taps, the other one element past a
+    tile edge (1029 = 2 x 512 + 5 and 16 x 64 + 5; 517 = 2 x 256 + 5 and 8 x 64 + 5; 70 x 516: 516 = 512 + 4 = 16 x 32 + 4), rows
+    of 1029 and 5 floats (element by element) and of 516 floats (16 bytes) on an aligned base and on one offset by a float.  Every
+    route gives the bits of the restated arithmetic and stays within the bound of the float64 model."""
+    from barc4dip_amd.metrics import local_contrast
+
+    p = prep()
+    rng = np.random.default_rng(28)
+    taps = {n: rng.uniform(0.2, 1.0, n) / n for n in (1, 9, 12, 49, 511)}
+    for shape in ((5, 1029), (517, 5), (70, 516)):
+        x = rng.poisson(40.0, shape).astype(np.float32)
+        off = _offset_by_one_float(x) if shape[1] % 4 == 0 else None
+        cases = [(taps[n], taps[n], ROUTES) for n in (1, 9, 12, 49)]
+        cases.append((taps[511], None, TWO_PASS) if shape[0] > shape[1] else (None, taps[511], TWO_PASS))
+        for wy, wx, routes in cases:
+            my, mx = (np.ones(1) if w is None else w for w in (wy, wx))
+            want = emulate_f32(x, my, mx, mode, 2.5)
+            within(want, M.model_separable(f64(x), my, mx, mode, 2.5), M.bound_separable(x, my, mx), f"{shape} {my.size} x {mx.size} taps {mode}")
+            for g in routes:
+                assert np.array_equal(p.separable_filter(x, wy, wx, mode=mode, cval=2.5, **g).view(np.uint32), want.view(np.uint32)), (shape, my.size, mx.size, g)
+                if off is not None:
+                    got = p.separable_filter(off, wy, wx, mode=mode, cval=2.5, **g)
+                    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (shape, my.size, mx.size, g, "offset base")
+        for size in (63, (3, 9)):
+            got, _ = local_case(x, size=size, mode=mode, cval=2.0)
+            if off is not None:
+                again = local_contrast(off, size, mode=mode, cval=2.0)
+                for k in got:
+                    assert np.array_equal(again[k].view(np.uint32), got[k].view(np.uint32)), (shape, size, k, "offset base")
+
+
 # ------------------------------------------------------------------------------------------------------------ 5: batches, widths
 @pytest.mark.parametrize("sigma,general", [(1.0, {}), (2.0, {"_general": True}), (2.0, {"_fused": True}), (10.0, {})])
 def test_batch_independence_and_access_widths(sigma, general):

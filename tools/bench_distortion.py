@@ -49,6 +49,7 @@ def _abi_call(x, field, order, mode="nearest"):
 
     from barc4dip_amd import _device as D
     from barc4dip_amd import _ffi
+    from barc4dip_amd._frames import mode_code
     from barc4dip_amd.preprocessing import distortion as DI
 
     lib, st = _ffi.lib(), _ffi.stream_ptr()
@@ -58,7 +59,7 @@ def _abi_call(x, field, order, mode="nearest"):
     coef = torch.empty((n, H + 2 * p, W + 2 * p), device="cuda") if order == 3 else None
     out = torch.empty((n, H, W), device="cuda")
     src = coef if order == 3 else x
-    m = DI.MODES[mode]
+    m = mode_code(mode)
     if isinstance(field, dict):
         f = DI._parse_field(field, tuple(x.shape))
         gy, gx = f["plane"]
