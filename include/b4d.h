@@ -803,6 +803,53 @@ int b4d_separable_filter(const float* in, int batch, int ny, int nx, const doubl
 int b4d_local_stats(const float* in, int batch, int ny, int nx, int size_y, int size_x, const double* taps_y, const double* taps_x,
                     int mode, float cval, float* mean, float* variance, float* contrast, void* stream);
 
+/* How close every frame of img (batch, ny, nx) float32 is to a reference frame (barc4dip_amd.metrics.perceptual; DESIGN.md
+ * section 28).  All pointers are DEVICE pointers except the taps (HOST float64, read before the call returns: they travel in the
+ * kernel arguments); asynchronous on `stream`, no synchronisation.  ref_stride is the element stride between reference frames:
+ * 0 = one reference frame serves the whole batch, ny * nx = the frames are paired (any stride >= ny * nx is taken).
+ * b4d_ssim: structural similarity (Wang et al. 2004) as scikit-image's structural_similarity forms it.  Window sizes (SciPy's
+ *   placement), taps, the two-dimensional padding by mode / cval and W are those of b4d_local_stats: NULL taps = box window (weights
+ *   1, W = size_y size_x), otherwise both float64 tap arrays.  Per output pixel five float64 sums over the window, along x, then
+ *   along y, in ascending tap order (box: s += v; taps: s = fma(w, v, s)): S_r, S_x, S_rr, S_xx, S_rx, the products r r, x x, r x
+ *   formed in float64, where they are exact.  Then, every operation a float64 operation of its own, in this order:
+ *       iw   = 1 / W  (the one division by W)            mu_r = S_r * iw          mu_x = S_x * iw
+ *       v_r  = cov_norm * (S_rr * iw - mu_r * mu_r)      v_x = cov_norm * (S_xx * iw - mu_x * mu_x)
+ *       v_rx = cov_norm * (S_rx * iw - mu_r * mu_x)      (variances are not clamped)
+ *       cs   = (2 * v_rx + c2) / (v_r + v_x + c2)
+ *       ssim = ((2 * (mu_r * mu_x) + c1) / (mu_r * mu_r + mu_x * mu_x + c1)) * cs
+ *   Identical frames give exactly 1; exchanging ref and img gives the same bits.  ssim_map, cs_map: (batch, ny, nx) float32 or
+ *   NULL.  means: (batch, 2) float64 or NULL, per frame the mean of the FLOAT64 ssim and cs over rows [crop_y, ny - crop_y) and
+ *   columns [crop_x, nx - crop_x): a workgroup (a 32 x 32 tile, 512 lanes; lane l holds column l % 32 and rows 2 (l / 32) and
+ *   2 (l / 32) + 1, added in that order) sums its pixels of the region by block_sum (down the wave, then the eight waves in order) into its slot of the
+ *   library's per-stream scratch buffer; a second launch gives lane l of 256 the tiles l, l + 256, .. of a frame in ascending
+ *   row-major order, adds the 256 lane sums by a halving tree (sh[l] += sh[l + o], o = 128 .. 1) and divides by the pixel count.
+ *   With only `means`, nothing of frame size is written.  NaN propagates: it poisons the maps over its footprint and the means of
+ *   its frame.
+ *   Window limit: 1 .. 63 per axis (B4D_EINVAL beyond) as far as one workgroup's LDS holds both staged tiles and five planes of
+ *   row sums: with rows = 31 + size_y,  8 * ceil4(rows * ceil4(31 + size_x)) + 1280 * rows + 128 <= 163840 bytes (B4D_ESIZE
+ *   beyond).  Every window up to 52 x 52 passes (33 x 33: 114 816 bytes), as do 63 x 25 and 48 x 63 (size_y x size_x); the default 11 x 11 takes
+ *   68 672 bytes, two workgroups a CU.
+ *   B4D_EINVAL: c1 <= 0, c2 <= 0, cov_norm <= 0 (or NaN), a negative crop, a crop that leaves no pixel while means is given, one
+ *   tap array without the other, all three outputs NULL, an output that overlaps an input, 0 < ref_stride < ny * nx.
+ * b4d_pair_errors: out (batch, 8) float64, per frame  sum (x - r)^2,  sum |x - r|,  max |x - r|,  sum r^2,  sum r,  min r,
+ *   max r,  sum x  (r the reference pixel, x the image pixel; differences and squares in float64).  The pixels of a frame are taken
+ *   in groups of four; workgroup s of split = min(1024, ceil(groups / 2048)) takes ceil(groups / split) consecutive groups, lane l
+ *   of it the groups l, l + 256, .. in ascending order; block_sum adds the lanes, the workgroup's row goes to the scratch buffer,
+ *   and a second launch merges the rows (lane l the rows l, l + 256, ..; then the halving tree above).  The split depends on
+ *   ny * nx alone and the walk not on the access width.  The extrema are exact.  They are merged by "take the newcomer if it is
+ *   smaller (larger) or a NaN"; a NaN that is held loses no comparison, so a NaN in r makes the sums of r, min r and max r NaN and
+ *   a NaN in r or x makes the sums and the maximum of the differences NaN (and sum x, if it is in x).
+ * b4d_pool2: out (batch, ny / 2, nx / 2), out[y, x] = ((in[2y, 2x] + in[2y, 2x + 1]) + (in[2y + 1, 2x] + in[2y + 1, 2x + 1]))
+ *   * 0.25f in float32, in that order; a trailing odd row or column is dropped.  ny < 2 or nx < 2: B4D_EINVAL.
+ * No atomics: a frame gives the same bits alone and inside any batch.  All argument errors are returned before any launch:
+ * B4D_EINVAL also for batch < 1, an empty shape, a null frame pointer, a mode out of range, in / out that overlap;
+ * B4D_ESIZE where ny * nx >= 2^31.                                                                                            */
+int b4d_ssim(const float* ref, long long ref_stride, const float* img, int batch, int ny, int nx, int size_y, int size_x,
+             const double* taps_y, const double* taps_x, int mode, float cval, double c1, double c2, double cov_norm, int crop_y,
+             int crop_x, float* ssim_map, float* cs_map, double* means, void* stream);
+int b4d_pair_errors(const float* ref, long long ref_stride, const float* img, int batch, int ny, int nx, double* out, void* stream);
+int b4d_pool2(const float* in, int batch, int ny, int nx, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
