@@ -127,6 +127,9 @@ SIGNATURES = {
     "b4d_ssim": (_i, [_vp, C.c_longlong, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _f, _d, _d, _d, _i, _i, _vp, _vp, _vp, _vp]),
     "b4d_pair_errors": (_i, [_vp, C.c_longlong, _vp, _i, _i, _i, _vp, _vp]),
     "b4d_pool2": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "b4d_tile_histogram": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "b4d_equalize_lut": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp]),
+    "b4d_lut_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

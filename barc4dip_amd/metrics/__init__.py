@@ -1,6 +1,6 @@
 """GPU drop-in for ``barc4dip.metrics`` (same public names as metrics/__init__.py:6-20) + temporal statistics, local contrast
 and, in ``perceptual`` (a module the reference names and leaves empty), the scores of a frame against a reference frame: SSIM,
-MS-SSIM, MSE / PSNR / NRMSE."""
+MS-SSIM, MSE / PSNR / NRMSE; frame and tile histograms."""
 from __future__ import annotations
 
 from . import kernels, multitau, sharpness, speckles, statistics, temporal, twotime
@@ -17,8 +17,10 @@ from . import contrast
 from .contrast import local_contrast
 from . import perceptual
 from .perceptual import frame_errors, ms_ssim, mse, nrmse, psnr, ssim
+from . import histogram
+from .histogram import frame_histogram
 
 __all__ = ["order", "temporal_median", "temporal_percentile", "temporal_robust_mean","sharpness", "sharpness_stats", "sharpness_stack_stats", "statistics", "speckles", "speckle_stats",
            "speckle_stack_stats", "distribution_moments", "temporal", "temporal_stats", "sharded", "kernels", "twotime",
            "two_time_correlation", "correlation_decay", "multitau", "multi_tau_correlation", "contrast", "local_contrast",
-           "perceptual", "ssim", "ms_ssim", "frame_errors", "mse", "psnr", "nrmse"]
+           "perceptual", "ssim", "ms_ssim", "frame_errors", "mse", "psnr", "nrmse", "histogram", "frame_histogram"]

@@ -850,6 +850,54 @@ int b4d_ssim(const float* ref, long long ref_stride, const float* img, int batch
 int b4d_pair_errors(const float* ref, long long ref_stride, const float* img, int batch, int ny, int nx, double* out, void* stream);
 int b4d_pool2(const float* in, int batch, int ny, int nx, float* out, void* stream);
 
+/* Histogram equalisation of every frame of in (batch, ny, nx) float32 (barc4dip_amd.preprocessing.enhancement, metrics.histogram;
+ * DESIGN.md section 29): contrast-limited adaptive equalisation by OpenCV's CPU rule (cv::CLAHE), cv::equalizeHist's rule at any
+ * depth, and the tile histograms behind both.  DEVICE pointers throughout, asynchronous on `stream`, no synchronisation, no
+ * allocation: the caller passes the workspaces.  Every float32 operation below is rounded on its own (the unit is compiled without
+ * contraction), every count is an integer: results are specified to the bit and a frame gives the same bits alone and in a batch.
+ *   levels L: 2 .. 65536.  tiles_x / tiles_y: tiles along x / along y (OpenCV's order), >= 1, tiles_x * tiles_y <= 4096.
+ *   qparams: (batch, 4) float32 per frame {lo, s, inv, unused}, 16-byte aligned.  s = float32(L / (float64(hi) - float64(lo))),
+ *   inv = float32((float64(hi) - float64(lo)) / (L - 1)); whole-number frames (uint8 / uint16 levels) take {0, 1, 1}.
+ *   s == 0 marks a frame that b4d_lut_apply copies unchanged.
+ * Quantiser: bin = clamp(floor((x - lo) * s), 0, L - 1).  The clamp is applied to the float before the conversion, so +-Inf and
+ *   products beyond the int range take the end bins and a NaN product (0 * Inf) bin 0; on every other value this is the
+ *   clamp(int(floor(.))) of the rule.  A NaN pixel has no bin.
+ * Tiles: an axis of n pixels and t tiles is extended by pad = (t - n % t) % t pixels behind its end, extended pixel e >= n
+ *   being pixel 2 (n - 1) - e (reflection without repeating the edge); pad <= n - 1 is required.  Tile side = (n + pad) / t; tile
+ *   area <= 2^24.  Extended pixels are counted; no padded copy is written.  Tiles of extended pixels only are legal.
+ * b4d_tile_histogram: counts (batch, tiles_y, tiles_x, L) uint32 = pixels of every tile per bin, n_valid (batch, tiles_y, tiles_x)
+ *   uint32 = non-NaN pixels of every tile.  One workgroup per tile up to L = 32768 (integer LDS atomics on min(16, 8192 / L)
+ *   copies of the histogram, added up on the way out); above, one workgroup per 32768-bin slice of a tile, which reads the tile
+ *   again.  Plain stores to memory.  16-byte loads from the first 16-byte boundary of every tile row on; its ragged ends and the
+ *   reflected columns one by one.
+ * b4d_equalize_lut: lut (batch, tiles, L) uint16 from counts and n_valid (tiles = tiles_y * tiles_x), one workgroup per tile.
+ *   A tile with n = n_valid == 0 gets lut[i] = i.
+ *   mode 0 (CLAHE): clip = 0 for clip_limit == 0, else c = clip_limit * n / L in float64 and clip = n where c >= n (nothing
+ *   exceeds it), else max(int(c), 1).  With clip > 0: excess = sum max(h[i] - clip, 0), h[i] = min(h[i], clip) + excess / L, and
+ *   with residual = excess % L > 0, step = max(L / residual, 1), one more in the bins i with i % step == 0 and
+ *   i / step < residual.  scale = float32(L - 1) / float32(n), lut[i] = clamp(rint(float32(sum_{j <= i} h[j]) * scale), 0, L - 1),
+ *   rint to even.
+ *   mode 1 (equalize_hist; tiles == 1): i0 = first non-empty bin; h[i0] == n (or n == 0) sets unchanged[frame] = 1 (else 0) and
+ *   the identity table; otherwise scale = float32(L - 1) / float32(n - h[i0]), lut[i <= i0] = 0 and
+ *   lut[i > i0] = clamp(rint(float32(sum_{i0 < j <= i} h[j]) * scale), 0, L - 1).  unchanged: (batch) int32, NULL in mode 0.
+ * b4d_lut_apply: out (batch, ny, nx) float32.  With th, tw the tile sides and inv_h = 1.0f / th: tyf = y * inv_h - 0.5f,
+ *   t1 = floor(tyf), ya = tyf - t1, ya1 = 1.0f - ya, tile rows max(t1, 0) and min(t1 + 1, tiles_y - 1); columns likewise.  With v
+ *   the four table entries at the pixel's bin, res = (v11 * xa1 + v12 * xa) * ya1 + (v21 * xa1 + v22 * xa) * ya, left to right.
+ *   flags bit 0 clear: out = clamp(rint(res), 0, L - 1); set: out = res * inv + lo.  flags bit 1 (one tile only): res = lut[bin]
+ *   without the interpolation, and frames with unchanged[frame] != 0 (unchanged may be NULL) are copied.  A NaN pixel and every
+ *   pixel of a frame with s == 0 is copied.  The row terms are formed once per row, the column terms once per lane for 16 rows;
+ *   16-byte accesses where nx % 4 == 0 and in / out are 16-byte aligned, the same bits otherwise.
+ * All argument errors are returned before any launch: B4D_EINVAL for a null pointer, batch < 1, an empty axis, tiles < 1, a
+ * padding longer than its axis less one, a mode or flags out of range, clip_limit < 0 or NaN, in / out that overlap, qparams off
+ * 16 bytes; B4D_ESIZE for levels outside 2 .. 65536, more than 4096 tiles, a tile of more than 2^24 pixels, ny * nx >= 2^31,
+ * batch > 65535.                                                                                                               */
+int b4d_tile_histogram(const float* in, int batch, int ny, int nx, int tiles_x, int tiles_y, int levels, const float* qparams,
+                       unsigned* counts, unsigned* n_valid, void* stream);
+int b4d_equalize_lut(const unsigned* counts, const unsigned* n_valid, int batch, int tiles, int levels, double clip_limit, int mode,
+                     unsigned short* lut, int* unchanged, void* stream);
+int b4d_lut_apply(const float* in, int batch, int ny, int nx, int tiles_x, int tiles_y, int levels, const float* qparams,
+                  const unsigned short* lut, const int* unchanged, int flags, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
