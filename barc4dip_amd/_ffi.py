@@ -130,6 +130,7 @@ SIGNATURES = {
     "b4d_tile_histogram": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "b4d_equalize_lut": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp]),
     "b4d_lut_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "b4d_spot_centroids": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _d, _d, _i, _d, _i, _d, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

@@ -1,11 +1,12 @@
 """GPU drop-in for ``barc4dip.signal`` (same public names as signal/__init__.py:6-26)."""
 from __future__ import annotations
 
-from . import corr, displacement, fft, focus, fringes, modal, scanning, speckle, stepping, tracking, wavefront
+from . import corr, displacement, fft, focus, fringes, hartmann, modal, scanning, speckle, stepping, tracking, wavefront
 from .corr import autocorr2d, autocorr2d_stack, psd_autocorr2d_stack, xcorr2d
 from .displacement import displacement_grid, displacement_map
 from .focus import beam_caustic, focal_spot, focus_geometry
 from .fringes import (coarse_carriers, fringe_carriers, fringe_demodulate, fringe_displacement, fringe_grid, phase_unwrap)
+from .hartmann import hartmann_cells, hartmann_displacement, hartmann_lattice, spot_centroids
 from .modal import modal_eval, modal_fit, modal_table
 from .scanning import speckle_scan
 from .speckle import speckle_contrast, speckle_imaging
@@ -28,4 +29,5 @@ __all__ = [
     "speckle", "speckle_contrast", "speckle_imaging",
     "stepping", "stepping_fit", "phase_stepping", "calibrate_steps", "stepping_displacement",
     "scanning", "speckle_scan",
+    "hartmann", "hartmann_cells", "spot_centroids", "hartmann_lattice", "hartmann_displacement",
 ]

@@ -169,3 +169,37 @@ def fringe_frame(shape, carriers, displacement=None, *, visibility=0.4, envelope
     if seed is not None:
         frame = np.random.default_rng(seed).poisson(frame).astype(np.float64)
     return frame
+
+
+def hartmann_frame(shape, pitch, origin=(0, 0), displacement=None, *, sigma: float = 2.0, amplitude: float = 1000.0,
+                   background: float = 0.0, seed=None) -> np.ndarray:
+    """Hartmann / Shack-Hartmann frame (H, W) float64: a Gaussian spot of ``amplitude`` and ``sigma`` px in every whole cell of
+    the lattice ``signal.hartmann_cells(shape, pitch, origin)``, at the cell's nominal position plus its displacement, on a
+    constant ``background``.
+
+    ``displacement``: ``None``, a ``(dy, dx)`` pair that broadcasts to the (gy, gx) lattice, or a callable of the nominal positions
+    ``(y, x)`` ((gy, 1) and (1, gx)) returning such a pair.  Every spot is drawn out to 8 sigma (1e-14 of its height).  With
+    ``seed`` the frame is Poisson noise of that intensity."""
+    from .signal.hartmann import hartmann_cells
+
+    H, W = (int(s) for s in shape)
+    cells = hartmann_cells((H, W), pitch, origin)
+    gy, gx = cells["shape"]
+    y0, x0 = cells["y"][:, None], cells["x"][None, :]
+    dy, dx = (0.0, 0.0) if displacement is None else (displacement(y0, x0) if callable(displacement) else displacement)
+    cy = np.broadcast_to(y0 + np.asarray(dy, dtype=np.float64), (gy, gx))
+    cx = np.broadcast_to(x0 + np.asarray(dx, dtype=np.float64), (gy, gx))
+    frame = np.full((H, W), float(background))
+    reach = 8.0 * float(sigma)
+    for i in range(gy):
+        for j in range(gx):
+            ya, yb = max(0, int(np.floor(cy[i, j] - reach))), min(H, int(np.ceil(cy[i, j] + reach)) + 1)
+            xa, xb = max(0, int(np.floor(cx[i, j] - reach))), min(W, int(np.ceil(cx[i, j] + reach)) + 1)
+            if ya >= yb or xa >= xb:
+                continue
+            ey = np.exp(-0.5 * ((np.arange(ya, yb) - cy[i, j]) / sigma) ** 2)
+            ex = np.exp(-0.5 * ((np.arange(xa, xb) - cx[i, j]) / sigma) ** 2)
+            frame[ya:yb, xa:xb] += amplitude * ey[:, None] * ex[None, :]
+    if seed is not None:
+        frame = np.random.default_rng(seed).poisson(frame).astype(np.float64)
+    return frame

@@ -898,6 +898,35 @@ int b4d_equalize_lut(const unsigned* counts, const unsigned* n_valid, int batch,
 int b4d_lut_apply(const float* in, int batch, int ny, int nx, int tiles_x, int tiles_y, int levels, const float* qparams,
                   const unsigned short* lut, const int* unchanged, int flags, float* out, void* stream);
 
+/* Hartmann sensor: spot centroids over a lattice of rectangular cells (barc4dip_amd.signal.hartmann).
+ * frames (batch, ny, nx): DEVICE float32.  y_edges (gy + 1), x_edges (gx + 1): HOST int32, ascending; cell (i, j) is the rows
+ * [y_edges[i], y_edges[i + 1]) by the columns [x_edges[j], x_edges[j + 1]), every side 2 .. 128, all cells inside the frame.  Pixels
+ * outside every cell are never read for a result.  out: DEVICE (batch, gy, gx, 14) float64, per cell
+ *   {cy, cx, flux, peak, peak_y, peak_x, background, noise, var_y, var_x, cov_yx, n_pixels, n_saturated, n_nan}.
+ * All arithmetic is float64 on the float32 pixels; NaN pixels take no part anywhere.  Positions are in frame coordinates.
+ *   peak: the largest value, at (peak_y, peak_x): first occurrence in row-major order within the cell (NaN x 3 in an all-NaN cell).
+ *   n_nan: NaN pixels.  n_saturated: pixels with v >= saturation (+inf disables it).
+ *   ring: the non-NaN pixels of the cell's one-pixel outer ring, m their mean; noise = sqrt(sum (v - m)^2 / n) over them, 0 where
+ *   n < 2; computed in every mode.
+ *   background b: background_mode 0: 0; 1: background_value; 2: the cell's minimum; 3: m.
+ *   t = b + threshold * (peak - b), 0 <= threshold < 1; weight w = v - t where that is > 0, else 0 (continuous in t).
+ *   n_pixels: pixels with w > 0.  flux F = sum w.  With (yc, xc) the cell's geometric centre ((first + last) / 2 per axis):
+ *   cy = yc + sum w (y - yc) / F, cx likewise; var_y = sum w (y - cy)^2 / F, var_x likewise, cov_yx = sum w (y - cy)(x - cx) / F.
+ *   A cell with F == 0 (constant, empty or all NaN) gets NaN in cy, cx and the three moments, 0 in flux and n_pixels.
+ *   method 1 (iteratively weighted centre of gravity): from that (cy, cx), `iterations` times
+ *   c <- centre + sum w g (p - centre) / sum w g with g = exp(-((y - cy)^2 + (x - cx)^2) / (2 sigma^2)) over the whole cell; cy, cx are
+ *   the last iterate, the other twelve quantities those of method 0.
+ * One workgroup stages a span of one cell row (its rows by a run of up to 16 neighbouring cells, at most 64 KiB) in LDS, so a
+ * frame is read once per call whatever `iterations` is: 16-byte loads from the first 16-byte boundary of a span row on where
+ * nx % 4 == 0 and frames is 16-byte aligned, the ragged ends and every other stack pixel by pixel.  One wave per cell: lane l adds
+ * the pixels l, l + 64, .. (row-major), then a fixed butterfly over the lanes: the same bits run to run, alone or in any batch.
+ * On `stream`; the edge tables are copied into the stream's scratch buffer.  B4D_EINVAL: null pointer, empty batch / frame /
+ * lattice, edges that do not ascend or leave the frame, a mode, threshold, method, sigma, iterations or saturation (NaN) out of
+ * range; B4D_ESIZE: a cell side outside 2 .. 128, gy > 65535, ny * nx >= 2^31.                                                  */
+int b4d_spot_centroids(const float* frames, int batch, int ny, int nx, const int32_t* y_edges, int gy, const int32_t* x_edges, int gx,
+                       int background_mode, double background_value, double threshold, int method, double sigma, int iterations,
+                       double saturation, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
