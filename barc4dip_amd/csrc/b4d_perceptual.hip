@@ -3,10 +3,11 @@
 // between the scales of MS-SSIM.  Frames are (batch, ny, nx) float32; the reference is one frame for the whole batch
 // (ref_stride 0) or one per frame.
 //
-// b4d_ssim is the pair form of k_local_stats (b4d_smooth.hip): both tiles with their halos in LDS as float32, five float64 row
-// sums (r, x, r r, x x, r x) per staged row, five float64 column sums per output pixel, every sum in ascending tap order.  The
-// taps travel in the kernel arguments.  No atomics anywhere: a workgroup writes its partial sums to its own slot of the per-stream
-// scratch buffer and a second launch adds the slots in a fixed order.
+// b4d_ssim is the pair form of k_local_stats (b4d_smooth.hip), and both stand on b4d_window.hpp: the stager, the taps in the kernel
+// arguments, the LDS layout, the row pass (five float64 sums r, x, r r, x x, r x per staged position) and the column pass (five
+// window sums per output pixel), every sum in ascending tap order.  This unit keeps the 512 lanes, the quotients and the means.
+// No atomics anywhere: a workgroup writes its partial sums to its own slot of the per-stream scratch buffer and a second launch
+// adds the slots in a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,23 +18,21 @@
 #include "b4d_common.hpp"
 #include "b4d_reduce.hpp"
 #include "b4d_tile.hpp"
+#include "b4d_window.hpp"
 
 // The quotients below are written as the header documents them, product by product: nothing is contracted into an FMA that the
-// text does not show (a contracted mu_r^2 + mu_x^2 would not be symmetric in r and x).  The explicit fma() calls stay.
+// text does not show (a contracted mu_r^2 + mu_x^2 would not be symmetric in r and x).  The pragma stands below the includes: the
+// sums of b4d_window.hpp are compiled as in b4d_smooth.hip (explicit fma() calls, exact products), this unit's own code is not contracted.
 #pragma clang fp contract(off)
 
 namespace b4d {
 
-// 32 x 32 outputs per workgroup, windows up to 63 per axis as far as the LDS holds them (lds_ssim)
-constexpr int PS_T = 32, PS_MAX = 63, PS_LANES = 512;
-constexpr size_t PS_LDS_LIMIT = 160 * 1024;
+// k_ssim: the 32 x 32 tiles and windows up to 63 per axis of b4d_window.hpp, as far as the LDS holds them; its own doubles behind
+// the row sums are block_sum's (two sums, a slot per wave)
+constexpr int PS_EXTRA = 2 * (WIN_PAIR_LANES / 64);
 // pair errors: a lane takes groups of four consecutive pixels; a workgroup at most PE_GROUPS of them per lane
 constexpr int PE_COLS = 8, PE_SUMS = 5, PE_GROUPS = 8, PE_MAX_SPLIT = 1024;
 
-struct TapsPair {
-    int sy, sx, box;
-    double wy[PS_MAX + 1], wx[PS_MAX + 1];
-};
 struct SsimArgs {
     const float* ref;   // of frame b0
     const float* img;
@@ -48,148 +47,37 @@ struct SsimArgs {
     int crop_y, crop_x;
 };
 
-constexpr int ps_up4(int n) { return (n + 3) & ~3; }
-
-// frame rows ys + [0, nrows) and columns xs + [0, ncols) -> lds (row pitch `pitch`) under the border rule, padded in two dimensions:
-// outside on either axis is cval under "constant".  The walk of 256 lanes (lane index t) is that of the separable filters' stager
-// (tile_walk): 16-byte loads for aligned groups of four inside a row, element by element for the others; the loads of a lane's
-// four (row, group) pairs are issued before the first value goes to LDS.
-__device__ __forceinline__ v4f load_group(const float* __restrict__ f, int ny, int nx, int yy, int xb, int mode, float cval, bool vec) {
-    v4f q = v4f{cval, cval, cval, cval};
-    if (yy >= 0) {
-        const float* row = f + (size_t)yy * nx;
-        if (vec && xb >= 0 && xb + 3 < nx) {
-            q = *reinterpret_cast<const v4f*>(row + xb);
-        } else {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int xx = border_index(xb + e, nx, mode);
-                if (xx >= 0) q[e] = row[xx];
-            }
-        }
-    }
-    return q;
-}
-__device__ __forceinline__ void stage_frame(float* __restrict__ lds, int pitch, const float* __restrict__ f, int ny, int nx, int ys, int nrows,
-                                            int xs, int ncols, int mode, float cval, bool vec, int t) {
-    const int xa = xs & ~3;
-    const int ng = (xs + ncols - xa + 3) >> 2;
-    TileWalk w = tile_walk(t, ng);
-    while (w.j < nrows) {
-        v4f q[4];
-        int at[4], c0[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            at[u] = -1;
-            if (w.j < nrows) {
-                const int xb = xa + 4 * w.g;
-                at[u] = w.j;
-                c0[u] = xb - xs;
-                q[u] = load_group(f, ny, nx, border_index(ys + w.j, ny, mode), xb, mode, cval, vec);
-            }
-            tile_step(w);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (at[u] >= 0) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = c0[u] + e;
-                    if (c >= 0 && c < ncols) lds[at[u] * pitch + c] = q[u][e];
-                }
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- SSIM
-// grid (tiles_x * tiles_y, frames), 512 lanes.  LDS: R, X, both tiles with their halos as float32 (PS_T + sy - 1 rows of pitch
-// up4(PS_T + sx - 1) each); B, five planes of float64 row sums (as many rows of PS_T: S_r, S_x, S_rr, S_xx, S_rx); sixteen doubles
-// for the workgroup's sums.  Lanes 0 .. 255 stage the reference tile, lanes 256 .. 511 the image tile.  Row pass: one lane forms
-// all five sums of a position, a tap costs two LDS reads for five FMAs.  Column pass: a lane forms the sums of two adjacent rows of
-// its column from one read of the sy + 1 rows of B below them (a box window has taps of 1.0: fma(1.0, v, s) is s + v).
-__global__ void __launch_bounds__(PS_LANES) k_ssim(SsimArgs a, TapsPair t) {
+// grid (tiles_x * tiles_y, frames), 512 lanes.  The pair user of b4d_window.hpp, which states the padding and the order of the
+// sums.  LDS by window_layout(2, 5, .., PS_EXTRA): R, X, both tiles with their halos as float32; five planes of float64 row sums (S_r,
+// S_x, S_rr, S_xx, S_rx); sixteen doubles for the workgroup's sums.  Lanes 0 .. 255 stage the reference tile, lanes 256 .. 511 the
+// image tile.  Row pass: one lane forms all five sums of a position, a tap costs two LDS reads for five FMAs.  Column pass: a lane
+// forms the sums of two adjacent rows of its column from one read of the sy + 1 rows of the planes below them.
+__global__ void __launch_bounds__(WIN_PAIR_LANES) k_ssim(SsimArgs a, WindowTaps t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int sy = t.sy, sx = t.sx, loy = sy / 2, lox = sx / 2;
-    const int pitch = ps_up4(PS_T + sx - 1), rows = PS_T + sy - 1;
-    const int plane_a = (rows * pitch + 3) & ~3, plane_b = rows * PS_T;
-    float* R = lds;
-    float* X = lds + plane_a;
-    double* B = reinterpret_cast<double*>(lds + 2 * plane_a);
-    double* sh = B + 5 * plane_b;
+    const WindowLayout l = window_layout(2, 5, sy, sx, PS_EXTRA);
+    double* B = reinterpret_cast<double*>(lds + l.sums);
+    double* sh = B + 5 * l.sum_plane;
     const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
-    const int x0 = tile_x * PS_T, y0 = tile_y * PS_T;
+    const int x0 = tile_x * WIN_T, y0 = tile_y * WIN_T;
     const size_t fo = (size_t)blockIdx.y * a.ny * a.nx;
-    const int tw = min(PS_T, a.nx - x0), th = min(PS_T, a.ny - y0);
+    const int tw = min(WIN_T, a.nx - x0), th = min(WIN_T, a.ny - y0);
     const int ha = th + sy - 1;
     if (threadIdx.x < 256)
-        stage_frame(R, pitch, a.ref + (size_t)a.ref_stride * blockIdx.y, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval,
-                    a.vec_ref != 0, threadIdx.x);
+        stage<NoSwz>(lds, l.pitch, a.ref + (size_t)a.ref_stride * blockIdx.y, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval,
+                     a.vec_ref != 0, threadIdx.x);
     else
-        stage_frame(X, pitch, a.img + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval, a.vec_img != 0, threadIdx.x - 256);
+        stage<NoSwz>(lds + l.plane, l.pitch, a.img + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval, a.vec_img != 0,
+                     threadIdx.x - 256);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < ha * PS_T; idx += PS_LANES) {
-        const int r = idx >> 5, c = idx & 31;
-        double s[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
-        if (c < tw) {
-            const float* pr = R + r * pitch + c;
-            const float* px = X + r * pitch + c;
-            if (t.box) {
-#pragma unroll 4
-                for (int k = 0; k < sx; ++k) {
-                    const double u = (double)pr[k], v = (double)px[k];
-                    s[0] += u;
-                    s[1] += v;
-                    s[2] = fma(u, u, s[2]);   // (the products of two float32 are exact in float64: s + u * u, rounded once)
-                    s[3] = fma(v, v, s[3]);
-                    s[4] = fma(u, v, s[4]);
-                }
-            } else {
-#pragma unroll 4
-                for (int k = 0; k < sx; ++k) {
-                    const double u = (double)pr[k], v = (double)px[k], w = t.wx[k];
-                    s[0] = fma(w, u, s[0]);
-                    s[1] = fma(w, v, s[1]);
-                    s[2] = fma(w, u * u, s[2]);
-                    s[3] = fma(w, v * v, s[3]);
-                    s[4] = fma(w, u * v, s[4]);
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 5; ++q) B[q * plane_b + idx] = s[q];
-    }
+    window_row_pass<2, WIN_PAIR_LANES>(lds, B, l, ha, tw, t);
     __syncthreads();
-    // W: the window's weight, summed as S_r of a frame of ones is
-    double W = (double)(sy * sx);
-    if (!t.box) {
-        double wx = 0.0;
-        for (int k = 0; k < sx; ++k) wx = fma(t.wx[k], 1.0, wx);
-        W = 0.0;
-        for (int j = 0; j < sy; ++j) W = fma(t.wy[j], wx, W);
-    }
-    const double iw = 1.0 / W;   // the one division by W: the five window means are products with it
+    const double iw = 1.0 / window_weight(t);   // the one division by W: the five window means are products with it
     const int c = threadIdx.x & 31, ox = x0 + c, ly = 2 * (threadIdx.x >> 5);
-    double s[2][5] = {{0.0, 0.0, 0.0, 0.0, 0.0}, {0.0, 0.0, 0.0, 0.0, 0.0}};
-    if (ly < th && ox < a.nx) {
-        const double* b = B + ly * PS_T + c;
-#pragma unroll 2
-        for (int j = 0; j <= sy; ++j) {   // row ly + j of B is tap j of output row ly and tap j - 1 of output row ly + 1
-            double v[5];
-#pragma unroll
-            for (int q = 0; q < 5; ++q) v[q] = b[q * plane_b + j * PS_T];
-            if (j < sy) {
-                const double w = t.wy[j];
-#pragma unroll
-                for (int q = 0; q < 5; ++q) s[0][q] = fma(w, v[q], s[0][q]);
-            }
-            if (j > 0) {
-                const double w = t.wy[j - 1];
-#pragma unroll
-                for (int q = 0; q < 5; ++q) s[1][q] = fma(w, v[q], s[1][q]);
-            }
-        }
-    }
+    WindowSums<5, 2> sums{};
+    if (ly < th && ox < a.nx) sums = window_col_sums<5, 2>(B + ly * WIN_T + c, l.sum_plane, t);
+    const auto& s = sums.s;
     double acc[2] = {0.0, 0.0};   // this lane's ssim and cs inside the region, the upper row first
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -210,7 +98,7 @@ __global__ void __launch_bounds__(PS_LANES) k_ssim(SsimArgs a, TapsPair t) {
         }
     }
     if (a.part) {   // (uniform: the whole workgroup calls)
-        block_sum(acc, sh, PS_LANES / 64);
+        block_sum(acc, sh, WIN_PAIR_LANES / 64);
         if (threadIdx.x == 0) {
             double* p = a.part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
             p[0] = acc[0];
@@ -370,12 +258,6 @@ __global__ void __launch_bounds__(256) k_pool2(const float* __restrict__ in, int
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// dynamic LDS of k_ssim: both staged tiles, the five planes of row sums, the workgroup's sums
-static size_t lds_ssim(int sy, int sx) {
-    const size_t rows = PS_T + sy - 1;
-    return 2 * sizeof(float) * ((rows * ps_up4(PS_T + sx - 1) + 3) & ~(size_t)3) + 5 * sizeof(double) * rows * PS_T + 2 * (PS_LANES / 64) * sizeof(double);
-}
-static unsigned tiles(int n, int t) { return (unsigned)((n + t - 1) / t); }
 // bytes of the reference: one frame, or batch frames ref_stride apart
 static size_t ref_bytes(long long ref_stride, int batch, size_t fpix) { return ((size_t)ref_stride * (batch - 1) + fpix) * sizeof(float); }
 static int check_ref(const char* fn, long long ref_stride, size_t fpix) {
@@ -393,12 +275,11 @@ extern "C" int b4d_ssim(const float* ref, long long ref_stride, const float* img
     if (const int rc = check_stack("b4d_ssim", "null input or empty shape", ref && img, batch, ny, nx, mode, true)) return rc;
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
     if (const int rc = check_ref("b4d_ssim", ref_stride, fpix)) return rc;
-    if (size_y < 1 || size_y > PS_MAX || size_x < 1 || size_x > PS_MAX)
-        return fail(B4D_EINVAL, "b4d_ssim: window sizes must be in 1 .. " + std::to_string(PS_MAX));
-    if (lds_ssim(size_y, size_x) > PS_LDS_LIMIT)
-        return fail(B4D_ESIZE, "b4d_ssim: a " + std::to_string(size_y) + " x " + std::to_string(size_x) + " window needs " +
-                                   std::to_string(lds_ssim(size_y, size_x)) + " bytes of LDS, more than " + std::to_string(PS_LDS_LIMIT));
-    if ((taps_y == nullptr) != (taps_x == nullptr)) return fail(B4D_EINVAL, "b4d_ssim: taps_y and taps_x must both be given or both be null");
+    if (const int rc = check_window("b4d_ssim", size_y, size_x, taps_y, taps_x)) return rc;
+    const size_t lds = window_layout(2, 5, size_y, size_x, PS_EXTRA).bytes;
+    if (lds > WIN_LDS_LIMIT)
+        return fail(B4D_ESIZE, "b4d_ssim: a " + std::to_string(size_y) + " x " + std::to_string(size_x) + " window needs " + std::to_string(lds) +
+                                   " bytes of LDS, more than " + std::to_string(WIN_LDS_LIMIT));
     if (!ssim_map && !cs_map && !means) return fail(B4D_EINVAL, "b4d_ssim: ssim_map, cs_map and means are all null");
     if (!(c1 > 0.0) || !(c2 > 0.0) || !(cov_norm > 0.0)) return fail(B4D_EINVAL, "b4d_ssim: c1, c2 and cov_norm must be > 0");
     if (crop_y < 0 || crop_x < 0) return fail(B4D_EINVAL, "b4d_ssim: negative crop");
@@ -412,19 +293,14 @@ extern "C" int b4d_ssim(const float* ref, long long ref_stride, const float* img
             ranges_overlap(ins[k], in_bytes[k], means, mbytes))
             return fail(B4D_EINVAL, "b4d_ssim: an output overlaps an input");
     hipStream_t st = (hipStream_t)stream;
-    TapsPair t{};
-    t.sy = size_y;
-    t.sx = size_x;
-    t.box = taps_y ? 0 : 1;
-    for (int k = 0; k < size_y; ++k) t.wy[k] = taps_y ? taps_y[k] : 1.0;
-    for (int k = 0; k < size_x; ++k) t.wx[k] = taps_x ? taps_x[k] : 1.0;
+    const WindowTaps t = fill_window_taps(size_y, size_x, taps_y, taps_x);
     SsimArgs a{};
     a.ref_stride = ref_stride;
     a.ny = ny;
     a.nx = nx;
     a.mode = mode;
     a.cval = cval;
-    a.tiles_x = (int)tiles(nx, PS_T);
+    a.tiles_x = (int)tiles(nx, WIN_T);
     a.vec_ref = vec_ok(ref, nx, 16) && ref_stride % 4 == 0;
     a.vec_img = vec_ok(img, nx, 16);
     a.c1 = c1;
@@ -432,7 +308,7 @@ extern "C" int b4d_ssim(const float* ref, long long ref_stride, const float* img
     a.cov_norm = cov_norm;
     a.crop_y = crop_y;
     a.crop_x = crop_x;
-    const unsigned ntiles = a.tiles_x * tiles(ny, PS_T);
+    const unsigned ntiles = a.tiles_x * tiles(ny, WIN_T);
     B4D_SCRATCH_LOCK();
     double* part = nullptr;
     if (means) {
@@ -446,7 +322,7 @@ extern "C" int b4d_ssim(const float* ref, long long ref_stride, const float* img
         a.ssim_map = ssim_map ? ssim_map + fpix * b0 : nullptr;
         a.cs_map = cs_map ? cs_map + fpix * b0 : nullptr;
         a.part = part ? part + (size_t)2 * ntiles * b0 : nullptr;
-        return launch(k_ssim, dim3(ntiles, nb), dim3(PS_LANES), lds_ssim(size_y, size_x), st, a, t);
+        return launch(k_ssim, dim3(ntiles, nb), dim3(WIN_PAIR_LANES), lds, st, a, t);
     });
     if (rc || !means) return rc;
     return launch(k_ssim_fin, dim3(batch), dim3(256), 0, st, part, (int)ntiles, (double)ry * (double)rx, means);

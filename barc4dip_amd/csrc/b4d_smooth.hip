@@ -9,6 +9,8 @@
 //                   kernel writes the output.  A lane produces 8 consecutive outputs along the filter axis from a register window
 //                   of 16 samples: one 16-byte LDS read feeds 32 (rows) or 128 (columns: four columns wide) FMAs.
 // Both routes add the products of one output in ascending tap order, so they give the same bits.
+// The stager of all four kernels (`stage`, with the NoSwz layout) and the core of k_local_stats -- taps, LDS layout, row pass; the column
+// pass by its contract, in loops of this kernel's own -- are b4d_window.hpp's, shared with k_ssim of b4d_perceptual.hip; Swz and Pair, the layouts of the separable kernels, stay here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +21,7 @@
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
 #include "b4d_tile.hpp"
+#include "b4d_window.hpp"
 
 namespace b4d {
 
@@ -37,8 +40,6 @@ constexpr int SR_TX = 512, SR_TY = 8;
 constexpr int SC_TX = 32, SC_TY = 256, SC_PITCH = SC_TX + 4;
 // fused kernel: 64 x 64 outputs per workgroup; the row pass gives 8 outputs across per lane, the column pass 4 columns x 4 rows
 constexpr int SF_T = 64, SF_PITCH_B = SF_T + 4;
-// local statistics: 32 x 32 outputs per workgroup, windows up to 63 x 63
-constexpr int LS_T = 32, LS_MAX = 63;
 
 struct Taps {   // one axis, float32, zero beyond n (never multiplied: 0 * NaN would widen a NaN's footprint)
     int n;
@@ -47,10 +48,6 @@ struct Taps {   // one axis, float32, zero beyond n (never multiplied: 0 * NaN w
 struct TapsFused {
     int ny, nx;
     float wy[SM_FUSED_PAD], wx[SM_FUSED_PAD];
-};
-struct TapsStats {
-    int sy, sx, box;
-    double wy[LS_MAX + 1], wx[LS_MAX + 1];
 };
 struct Frame {   // what every kernel needs of the call
     const float* in;
@@ -61,10 +58,9 @@ struct Frame {   // what every kernel needs of the call
     float eps;
 };
 
-constexpr int up4(int n) { return (n + 3) & ~3; }
 constexpr int up8(int n) { return (n + 7) & ~7; }
 
-// Where sample (row j, column c) of a staged tile lives in LDS.
+// Where sample (row j, column c) of a staged tile lives in LDS (NoSwz, plain rows: b4d_window.hpp).
 // Swz: rows of 8-output lanes that read 16 bytes at a time: four words of padding behind every 128 columns, so that lanes 16 apart
 //   (128 words: the same bank without it) meet on one bank less often.  Monotonic; an aligned group of eight stays adjacent.
 //   A row of w columns takes swz_width(w) words.
@@ -75,65 +71,12 @@ struct Swz {
     __device__ static __forceinline__ int col(int c) { return c + ((c >> 7) << 2); }
     __device__ static __forceinline__ int at(int j, int c, int pitch) { return j * pitch + col(c); }
 };
-struct NoSwz {
-    __device__ static __forceinline__ int at(int j, int c, int pitch) { return j * pitch + c; }
-};
 struct Pair {
     __device__ static __forceinline__ int col(int c2) { return c2 + ((c2 >> 6) << 2); }
     __device__ static __forceinline__ int at(int j, int c, int pitch) { return (j >> 1) * pitch + col(2 * c) + (j & 1); }
 };
 constexpr int swz_width(int w) { return w + ((w >> 7) << 2) + 4; }
 constexpr int pair_width(int w) { return 2 * w + ((2 * w >> 6) << 2) + 4; }
-
-// frame rows ys + [0, nrows) and columns xs + [0, ncols) -> lds[S::at(j, c, pitch)], under the border rule; 16-byte loads for
-// aligned groups of four inside a row (vec: nx % 4 == 0 and an aligned base), element by element for the others.  A lane walks the
-// (row, group) pairs 256 apart without a division per pair, four pairs at a time: their loads are all issued before the first
-// value goes to LDS.
-template <class S>
-__device__ __forceinline__ void stage(float* __restrict__ lds, int pitch, const float* __restrict__ f, int ny, int nx, int ys, int nrows, int xs,
-                                      int ncols, int mode, float cval, bool vec) {
-    const int xa = xs & ~3;
-    const int ng = (xs + ncols - xa + 3) >> 2;
-    TileWalk w = tile_walk(threadIdx.x, ng);
-    while (w.j < nrows) {
-        v4f q[4];
-        int at[4], c0[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            at[u] = -1;
-            q[u] = v4f{cval, cval, cval, cval};
-            if (w.j < nrows) {
-                const int yy = border_index(ys + w.j, ny, mode);
-                const int xb = xa + 4 * w.g;
-                at[u] = w.j;
-                c0[u] = xb - xs;
-                if (yy >= 0) {
-                    const float* row = f + (size_t)yy * nx;
-                    if (vec && xb >= 0 && xb + 3 < nx) {
-                        q[u] = *reinterpret_cast<const v4f*>(row + xb);
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            const int xx = border_index(xb + e, nx, mode);
-                            if (xx >= 0) q[u][e] = row[xx];
-                        }
-                    }
-                }
-            }
-            tile_step(w);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (at[u] >= 0) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int c = c0[u] + e;
-                    if (c >= 0 && c < ncols) lds[S::at(at[u], c, pitch)] = q[u][e];
-                }
-            }
-        }
-    }
-}
 
 // ---------------------------------------------------------------------------------------------- register windows
 // A lane's R outputs along the filter axis, acc[j] = sum_k w[k] * s[j + k] with k ascending, from a window of 2 R samples in
@@ -231,7 +174,7 @@ __global__ void __launch_bounds__(256) k_smooth_row(Frame a, Taps t) {
     const int x0 = tile_x * SR_TX, y0 = tile_y * SR_TY;
     const size_t fo = (size_t)blockIdx.y * a.ny * a.nx;
     const int tw = min(SR_TX, a.nx - x0), th = min(SR_TY, a.ny - y0);
-    stage<Pair>(lds, pitch, a.in + fo, a.ny, a.nx, y0, th, x0 - lo, tw + n - 1, a.mode, a.cval, a.vec_in != 0);
+    stage<Pair>(lds, pitch, a.in + fo, a.ny, a.nx, y0, th, x0 - lo, tw + n - 1, a.mode, a.cval, a.vec_in != 0, threadIdx.x);
     __syncthreads();
     const int lx = threadIdx.x & 63, ly = 2 * (threadIdx.x >> 6), ox = x0 + 8 * lx;
     if (ox >= a.nx || ly >= th) return;
@@ -264,7 +207,7 @@ __global__ void __launch_bounds__(256) k_smooth_col(Frame a, const float* __rest
     const int x0 = tile_x * SC_TX, y0 = tile_y * SC_TY;
     const size_t fo = (size_t)blockIdx.y * a.ny * a.nx;
     const int tw = min(SC_TX, a.nx - x0), th = min(SC_TY, a.ny - y0);
-    stage<NoSwz>(lds, SC_PITCH, a.in + fo, a.ny, a.nx, y0 - lo, th + n - 1, x0, tw, a.mode, a.cval, a.vec_in != 0);
+    stage<NoSwz>(lds, SC_PITCH, a.in + fo, a.ny, a.nx, y0 - lo, th + n - 1, x0, tw, a.mode, a.cval, a.vec_in != 0, threadIdx.x);
     __syncthreads();
     const int lx = threadIdx.x & 7, r0 = 8 * (threadIdx.x >> 3), ox = x0 + 4 * lx;
     if (ox >= a.nx || r0 >= th) return;
@@ -307,7 +250,7 @@ __global__ void __launch_bounds__(256) k_smooth_fused(Frame a, TapsFused t) {
     const size_t fo = (size_t)blockIdx.y * a.ny * a.nx;
     const int tw = min(SF_T, a.nx - x0), th = min(SF_T, a.ny - y0);
     const int ha = th + ny_t - 1;
-    stage<Swz>(A, pitch_a, a.in + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + nx_t - 1, a.mode, a.cval, a.vec_in != 0);
+    stage<Swz>(A, pitch_a, a.in + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + nx_t - 1, a.mode, a.cval, a.vec_in != 0, threadIdx.x);
     __syncthreads();
     const bool id_x = nx_t == 1 && t.wx[0] == 1.f, id_y = ny_t == 1 && t.wy[0] == 1.f;
     for (int idx = threadIdx.x; idx < ha * (SF_T / 8); idx += 256) {
@@ -347,69 +290,43 @@ __global__ void __launch_bounds__(256) k_smooth_fused(Frame a, TapsFused t) {
 }
 
 // ---------------------------------------------------------------------------------------------- local statistics
-// grid (tiles_x * tiles_y, frames).  LDS: A, the tile with its halo as float32 (LS_T + sy - 1 rows of pitch up4(LS_T + sx - 1)); B1, B2,
-// the float64 row sums of x and x * x (as many rows of LS_T).  The frame is padded in two dimensions ("constant": cval everywhere
-// outside), so every sum is over the sy x sx window of the padded frame.  All sums in ascending tap order.  One sum per lane and
-// LDS value: a lane that forms four adjacent sums from one read of each value was measured 1.3 - 1.8 x slower (a quarter of the
-// lanes, each four times as long).
-__global__ void __launch_bounds__(256) k_local_stats(Frame a, float* __restrict__ var_out, float* __restrict__ con_out, TapsStats t) {
+// grid (tiles_x * tiles_y, frames).  The one-frame user of b4d_window.hpp, which states the padding and the order of the sums: A,
+// the tile with its halo as float32, and the float64 row sums of x and x * x, laid out by window_layout(1, 2, ..).  One sum per lane
+// and LDS value: a lane that forms four adjacent sums from one read of each value was measured 1.3 - 1.8 x slower (a quarter of
+// the lanes, each four times as long).
+__global__ void __launch_bounds__(256) k_local_stats(Frame a, float* __restrict__ var_out, float* __restrict__ con_out, WindowTaps t) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int sy = t.sy, sx = t.sx, loy = sy / 2, lox = sx / 2;
-    const int pitch_a = up4(LS_T + sx - 1), rows = LS_T + sy - 1;
+    const WindowLayout l = window_layout(1, 2, sy, sx, 0);
     float* A = lds;
-    double* B1 = reinterpret_cast<double*>(lds + ((rows * pitch_a + 3) & ~3));
-    double* B2 = B1 + rows * LS_T;
+    double* B = reinterpret_cast<double*>(lds + l.sums);
     const int tile_y = blockIdx.x / a.tiles_x, tile_x = blockIdx.x - tile_y * a.tiles_x;
-    const int x0 = tile_x * LS_T, y0 = tile_y * LS_T;
+    const int x0 = tile_x * WIN_T, y0 = tile_y * WIN_T;
     const size_t fo = (size_t)blockIdx.y * a.ny * a.nx;
-    const int tw = min(LS_T, a.nx - x0), th = min(LS_T, a.ny - y0);
+    const int tw = min(WIN_T, a.nx - x0), th = min(WIN_T, a.ny - y0);
     const int ha = th + sy - 1;
-    stage<NoSwz>(A, pitch_a, a.in + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval, a.vec_in != 0);
+    stage<NoSwz>(A, l.pitch, a.in + fo, a.ny, a.nx, y0 - loy, ha, x0 - lox, tw + sx - 1, a.mode, a.cval, a.vec_in != 0, threadIdx.x);
     __syncthreads();
-    for (int idx = threadIdx.x; idx < ha * LS_T; idx += 256) {
-        const int r = idx >> 5, c = idx & 31;
-        double s1 = 0.0, s2 = 0.0;
-        if (c < tw) {
-            const float* p = A + r * pitch_a + c;
-            if (t.box) {
-                for (int k = 0; k < sx; ++k) {
-                    const double x = (double)p[k];
-                    s1 += x;
-                    s2 += x * x;
-                }
-            } else {
-                for (int k = 0; k < sx; ++k) {
-                    const double x = (double)p[k];
-                    s1 = fma(t.wx[k], x, s1);
-                    s2 = fma(t.wx[k], x * x, s2);
-                }
-            }
-        }
-        B1[idx] = s1;
-        B2[idx] = s2;
-    }
+    window_row_pass<1, 256>(A, B, l, ha, tw, t);
     __syncthreads();
-    // W: the window's weight, summed as S1 of a frame of ones is
-    double W = (double)(sy * sx);
-    if (!t.box) {
-        double wx = 0.0;
-        for (int k = 0; k < sx; ++k) wx = fma(t.wx[k], 1.0, wx);
-        W = 0.0;
-        for (int j = 0; j < sy; ++j) W = fma(t.wy[j], wx, W);
-    }
+    const double W = window_weight(t);
     const int c = threadIdx.x & 31, ox = x0 + c;
     if (ox >= a.nx) return;
     for (int ly = threadIdx.x >> 5; ly < th; ly += 8) {
+        // the column pass as b4d_window.hpp states it (window_col_sums<2, 1> gives the same bits); the loops are this kernel's own
+        // because box 7 x 7 ran 0.7 % slower on the shared function, outside the parent's spread
         double s1 = 0.0, s2 = 0.0;
+        const double* B1 = B;
+        const double* B2 = B + l.sum_plane;
         if (t.box) {
             for (int j = 0; j < sy; ++j) {
-                s1 += B1[(ly + j) * LS_T + c];
-                s2 += B2[(ly + j) * LS_T + c];
+                s1 += B1[(ly + j) * WIN_T + c];
+                s2 += B2[(ly + j) * WIN_T + c];
             }
         } else {
             for (int j = 0; j < sy; ++j) {
-                s1 = fma(t.wy[j], B1[(ly + j) * LS_T + c], s1);
-                s2 = fma(t.wy[j], B2[(ly + j) * LS_T + c], s2);
+                s1 = fma(t.wy[j], B1[(ly + j) * WIN_T + c], s1);
+                s2 = fma(t.wy[j], B2[(ly + j) * WIN_T + c], s2);
             }
         }
         const double m = s1 / W;
@@ -429,11 +346,6 @@ static void round_taps(const double* w, int n, float* dst, int cap) {
 static size_t lds_row(int n) { return sizeof(float) * (SR_TY / 2) * (size_t)pair_width(SR_TX + up8(n)); }
 static size_t lds_col(int n) { return sizeof(float) * SC_PITCH * (size_t)(SC_TY + up8(n)); }
 static size_t lds_fused(int n_y, int n_x) { return sizeof(float) * (size_t)(SF_T + up4(n_y)) * (swz_width(SF_T + up8(n_x)) + SF_PITCH_B); }
-static size_t lds_stats(int sy, int sx) {
-    const size_t rows = LS_T + sy - 1;
-    return sizeof(float) * ((rows * up4(LS_T + sx - 1) + 3) & ~(size_t)3) + 2 * sizeof(double) * rows * LS_T;
-}
-static unsigned tiles(int n, int t) { return (unsigned)((n + t - 1) / t); }
 
 }  // namespace b4d
 
@@ -519,31 +431,25 @@ extern "C" int b4d_separable_filter(const float* in, int batch, int ny, int nx, 
 extern "C" int b4d_local_stats(const float* in, int batch, int ny, int nx, int size_y, int size_x, const double* taps_y, const double* taps_x,
                                int mode, float cval, float* mean, float* variance, float* contrast, void* stream) {
     if (const int rc = check_stack("b4d_local_stats", "null input or empty shape", in, batch, ny, nx, mode, true)) return rc;
-    if (size_y < 1 || size_y > LS_MAX || size_x < 1 || size_x > LS_MAX)
-        return fail(B4D_EINVAL, "b4d_local_stats: window sizes must be in 1 .. " + std::to_string(LS_MAX));
-    if ((taps_y == nullptr) != (taps_x == nullptr)) return fail(B4D_EINVAL, "b4d_local_stats: taps_y and taps_x must both be given or both be null");
+    if (const int rc = check_window("b4d_local_stats", size_y, size_x, taps_y, taps_x)) return rc;
     if (!mean && !variance && !contrast) return fail(B4D_EINVAL, "b4d_local_stats: mean, variance and contrast are all null");
     const size_t fpix = (size_t)ny * nx, bytes = fpix * batch * sizeof(float);
     if (ranges_overlap(in, bytes, mean, bytes) || ranges_overlap(in, bytes, variance, bytes) || ranges_overlap(in, bytes, contrast, bytes))
         return fail(B4D_EINVAL, "b4d_local_stats: an output overlaps the input");
     hipStream_t st = (hipStream_t)stream;
-    TapsStats t{};
-    t.sy = size_y;
-    t.sx = size_x;
-    t.box = taps_y ? 0 : 1;
-    for (int k = 0; k < size_y; ++k) t.wy[k] = taps_y ? taps_y[k] : 1.0;
-    for (int k = 0; k < size_x; ++k) t.wx[k] = taps_x ? taps_x[k] : 1.0;
+    const WindowTaps t = fill_window_taps(size_y, size_x, taps_y, taps_x);
+    const size_t lds = window_layout(1, 2, size_y, size_x, 0).bytes;
     Frame a{};
     a.ny = ny;
     a.nx = nx;
     a.mode = mode;
     a.cval = cval;
-    a.tiles_x = (int)tiles(nx, LS_T);
+    a.tiles_x = (int)tiles(nx, WIN_T);
     a.vec_in = vec_ok(in, nx, 16);
     return for_frame_chunks(batch, MAX_GRID_FRAMES, [&](int b0, int nb) {
         a.in = in + fpix * b0;
         a.out = mean ? mean + fpix * b0 : nullptr;
-        return launch(k_local_stats, dim3(a.tiles_x * tiles(ny, LS_T), nb), dim3(256), lds_stats(size_y, size_x), st, a,
+        return launch(k_local_stats, dim3(a.tiles_x * tiles(ny, WIN_T), nb), dim3(256), lds, st, a,
                       variance ? variance + fpix * b0 : nullptr, contrast ? contrast + fpix * b0 : nullptr, t);
     });
 }

@@ -1,12 +1,15 @@
-// b4d_tile.hpp -- what a tiled kernel over a (batch, ny, nx) float32 stack needs (b4d_rankfilt.hip, b4d_smooth.hip; the mode codes
-// also b4d_warp.hip): the border rule, the division-free walk of a workgroup over a tile's groups, the four-wide stores, and the
-// argument check, alignment predicate and frame-chunk loop of the entry points (the two units keep their
-// own stagers, and why).  The border rule and the walk are __host__ __device__ and free of HIP types, so a plain C++ program can
-// include this header and run them (tests/test_rank_filter_host.py, tests/test_tile_walk_host.py); everything else needs hipcc.
+// b4d_tile.hpp -- what a tiled kernel over a (batch, ny, nx) float32 stack needs (b4d_rankfilt.hip, b4d_smooth.hip,
+// b4d_perceptual.hip; the mode codes also b4d_warp.hip): the border rule, the division-free walk of a workgroup over a tile's
+// groups, the four-wide stores, and the argument check, alignment predicate, tile count and frame-chunk loop of the entry points
+// (the rank filters keep their own stager, and why; the other one is `stage` of b4d_window.hpp).  The border
+// rule and the walk are __host__ __device__ and free of HIP types, so a plain C++ program can include this header and run them
+// (tests/test_rank_filter_host.py, tests/test_tile_walk_host.py); everything below them needs hipcc.
 #pragma once
 #include "b4d_keys.hpp"   // B4D_HD
 
 namespace b4d {
+
+constexpr int up4(int n) { return (n + 3) & ~3; }
 
 // source index of position i on an axis of n samples under scipy.ndimage's border modes, for any overhang (repeated
 // reflection / wrap); -1 = outside (mode "constant").  The codes of every entry point that takes a mode: b4d_warp_* knows 0 .. 3.
@@ -28,8 +31,8 @@ B4D_HD int border_index(int i, int n, int mode) {
 
 // The walk of 256 lanes over the (row j, group g) pairs of a tile with ng groups of four columns a row: lane t takes the pairs
 // t, t + 256, t + 512, .. of the row-major order.  One division per lane, none per pair: 256 = dq * ng + dr, so a step adds dq rows
-// and dr groups and carries once.  Its one user is `stage` of b4d_smooth.hip; it sits here, outside any .hip file, so that a host
-// program can run it for every lane and tile shape.
+// and dr groups and carries once.  Its one user is `stage` of b4d_window.hpp (separable filters, local statistics, SSIM); it is host
+// code, so that a program can run it for every lane and tile shape.
 struct TileWalk {
     int j, g, ng, dq, dr;
 };
@@ -92,6 +95,8 @@ inline int check_stack(const char* fn, const char* what, bool ptrs, int batch, i
 }
 // whether rows of nx elements behind p take accesses of four elements, `bytes` wide (every row then starts on a multiple of it)
 inline bool vec_ok(const void* p, int nx, size_t bytes) { return p && nx % 4 == 0 && ptr_aligned(p, bytes); }
+// tiles of edge t along an axis of n
+static unsigned tiles(int n, int t) { return (unsigned)((n + t - 1) / t); }
 // f(b0, nb) for every chunk of at most `chunk` frames (a grid dimension holds 65535); stops at the first error
 constexpr int MAX_GRID_FRAMES = 65535;
 template <class F>

@@ -203,8 +203,7 @@ def test_lds_formula_and_window_limit():
     assert all(P.lds_bytes(sy, sx) <= P.LDS_LIMIT for sy in range(1, 53) for sx in range(1, 53))
     assert P.lds_bytes(53, 53) > P.LDS_LIMIT and P.lds_bytes(63, 25) <= P.LDS_LIMIT < P.lds_bytes(63, 26)
     assert P.lds_bytes(48, 63) <= P.LDS_LIMIT < P.lds_bytes(49, 63)
-    src = open(os.path.join(ROOT, "barc4dip_amd", "csrc", "b4d_perceptual.hip")).read()
-    assert "PS_LDS_LIMIT = 160 * 1024" in src and "PS_T = 32, PS_MAX = 63, PS_LANES = 512" in src
+    # that the kernel's layout and constants are these: tests/test_window_core_host.py, which runs csrc/b4d_window.hpp
 
 
 def test_wiring():

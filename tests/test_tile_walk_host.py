@@ -1,6 +1,6 @@
 """The walk of csrc/b4d_tile.hpp (tile_walk, tile_step: which (row, group-of-four) pairs of a tile each of the 256 lanes of a
 workgroup takes), run as host code by a small C++ program in two forms: rounds of U = 4 groups until the lane has left the tile
-(`stage` of b4d_smooth.hip: separable filters, local statistics), and one round of U = 6 or 7 over a lane's whole share (the form
+(`stage` of b4d_window.hpp: separable filters, local statistics, SSIM), and one round of U = 6 or 7 over a lane's whole share (the form
 of a fully unrolled fill; no kernel runs the walk that way yet: `fill_tile` of b4d_rankfilt.hip still divides per group).  Every
 pair of the tile must be visited exactly once and nothing else.  The border rule of the same header is covered by
 tests/test_rank_filter_host.py (test_border_index_equals_numpy_pad)."""
