@@ -131,6 +131,9 @@ SIGNATURES = {
     "b4d_equalize_lut": (_i, [_vp, _vp, _i, _i, _i, _d, _i, _vp, _vp, _vp]),
     "b4d_lut_apply": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "b4d_spot_centroids": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _d, _d, _i, _d, _i, _d, _vp, _vp]),
+    "b4d_label_regions": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "b4d_region_properties": (_i, [_vp, _vp, _i, _i, _i, _vp, _d, _d, _vp, _vp]),
+    "b4d_relabel": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "b4d_uw_step":(_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_ulonglong, _i, _i, C.c_float, C.c_float, _i, _i, _vp, _vp]),
 }
 

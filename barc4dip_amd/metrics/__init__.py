@@ -19,8 +19,10 @@ from . import perceptual
 from .perceptual import frame_errors, ms_ssim, mse, nrmse, psnr, ssim
 from . import histogram
 from .histogram import frame_histogram
+from . import regions
+from .regions import find_spots, region_properties
 
 __all__ = ["order", "temporal_median", "temporal_percentile", "temporal_robust_mean","sharpness", "sharpness_stats", "sharpness_stack_stats", "statistics", "speckles", "speckle_stats",
            "speckle_stack_stats", "distribution_moments", "temporal", "temporal_stats", "sharded", "kernels", "twotime",
            "two_time_correlation", "correlation_decay", "multitau", "multi_tau_correlation", "contrast", "local_contrast",
-           "perceptual", "ssim", "ms_ssim", "frame_errors", "mse", "psnr", "nrmse", "histogram", "frame_histogram"]
+           "perceptual", "ssim", "ms_ssim", "frame_errors", "mse", "psnr", "nrmse", "histogram", "frame_histogram", "regions", "region_properties", "find_spots"]

@@ -203,3 +203,39 @@ def hartmann_frame(shape, pitch, origin=(0, 0), displacement=None, *, sigma: flo
     if seed is not None:
         frame = np.random.default_rng(seed).poisson(frame).astype(np.float64)
     return frame
+
+
+def spot_field(shape, n: int, *, seed: int, sigma: float = 2.0, amplitude: float = 1000.0, background: float = 0.0, noise: float = 0.0,
+               min_separation=None):
+    """Gaussian spots at random positions that lie on no lattice: (frame (H, W) float64, centres (n, 2) float64 rows (y, x)).
+
+    The centres are drawn one by one, uniformly and at sub-pixel positions, at least ``min_separation`` px (``None``: 8 sigma)
+    from each other and half of that from the frame's edges; each spot has ``amplitude`` and ``sigma`` px and is drawn out to
+    8 sigma, on a constant ``background``, plus Gaussian noise of standard deviation ``noise``.  ValueError where ``n`` spots do
+    not fit."""
+    H, W = (int(s) for s in shape)
+    sep = 8.0 * float(sigma) if min_separation is None else float(min_separation)
+    if n < 0 or sigma <= 0 or sep < 0 or H <= sep or W <= sep:
+        raise ValueError(f"cannot place {n} spots of sigma {sigma} at separation {sep} on {(H, W)}")
+    rng = np.random.default_rng(seed)
+    centres = np.empty((n, 2))
+    k = tries = 0
+    while k < n:
+        tries += 1
+        if tries > 1000 * (n + 1):
+            raise ValueError(f"{n} spots at separation {sep} do not fit on {(H, W)}")
+        c = np.array([rng.uniform(0.5 * sep, H - 1 - 0.5 * sep), rng.uniform(0.5 * sep, W - 1 - 0.5 * sep)])
+        if k == 0 or np.min(np.hypot(*(centres[:k] - c).T)) >= sep:
+            centres[k] = c
+            k += 1
+    frame = np.full((H, W), float(background))
+    reach = 8.0 * float(sigma)
+    for cy, cx in centres:
+        ya, yb = max(0, int(np.floor(cy - reach))), min(H, int(np.ceil(cy + reach)) + 1)
+        xa, xb = max(0, int(np.floor(cx - reach))), min(W, int(np.ceil(cx + reach)) + 1)
+        ey = np.exp(-0.5 * ((np.arange(ya, yb) - cy) / sigma) ** 2)
+        ex = np.exp(-0.5 * ((np.arange(xa, xb) - cx) / sigma) ** 2)
+        frame[ya:yb, xa:xb] += amplitude * ey[:, None] * ex[None, :]
+    if noise:
+        frame = frame + rng.normal(0.0, float(noise), (H, W))
+    return frame, centres

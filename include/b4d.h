@@ -31,6 +31,7 @@ extern "C" {
 #define B4D_ESIZE (-2)    /* (ny, nx) not supported by the compiled kernels */
 #define B4D_EHIP (-3)     /* a HIP runtime call failed */
 #define B4D_ENOMEM (-4)
+#define B4D_ELOOP (-5)    /* a loop bound of the labelling kernels was reached (reported in n_regions, see b4d_label_regions) */
 
 /* flags for b4d_autocorr2 / b4d_psd_autocorr2 (signal/corr.py:169-180 keyword arguments) */
 #define B4D_REMOVE_MEAN 1u      /* remove_mean=True  : zero the DC bin of the power spectrum */
@@ -926,6 +927,54 @@ int b4d_lut_apply(const float* in, int batch, int ny, int nx, int tiles_x, int t
 int b4d_spot_centroids(const float* frames, int batch, int ny, int nx, const int32_t* y_edges, int gy, const int32_t* x_edges, int gx,
                        int background_mode, double background_value, double threshold, int method, double sigma, int iterations,
                        double saturation, double* out, void* stream);
+
+/* Regions: connected-component labelling, per-region measurements, relabelling (barc4dip_amd.geometry.labels,
+ * barc4dip_amd.metrics.regions).  Device pointers, the caller's stream, nothing synchronises.
+ * b4d_label_regions: exactly one of frames (batch, ny, nx) DEVICE float32 with thresholds (batch) DEVICE float32, and mask
+ *   (batch, ny, nx) DEVICE bytes, is non-NULL.  Foreground: frames[p] > thresholds[frame], strict (a NaN is background, +inf is
+ *   foreground), or mask[p] != 0.  connectivity 1: pixels that share an edge are connected; 2: an edge or a corner.
+ *   labels (batch, ny, nx) DEVICE int32: 0 on the background, 1 .. N on the foreground; two foreground pixels have the same label
+ *   if and only if they are connected; the labels of a frame are numbered in the raster order of each component's first pixel
+ *   (scipy.ndimage.label with generate_binary_structure(2, connectivity)).  n_regions (batch) DEVICE int32: N per frame.
+ *   Integers throughout: the same result for a frame alone and in any batch, run after run.
+ *   Passes (separate launches, no workgroup waits for another): union-find over 32 x 64 tiles in LDS (links point to a smaller
+ *   raster index, the root of a set is its smallest; integer atomicMin), a pass over the tile seams (tile-corner diagonals
+ *   included), a flatten pass, an exclusive scan of the root flags in blocks of 2048 pixels, the roots' numbers, every pixel's
+ *   number from its root.  labels is the only frame-sized array; the stream's scratch buffer takes batch * ceil(ny nx / 2048)
+ *   words.  Every find and every retry ends by construction (links strictly decrease) and carries an explicit bound, the number
+ *   of cells; a bound that is reached sets an error word, and every frame of the call then gets n_regions = B4D_ELOOP (labels
+ *   unspecified): the call has returned B4D_OK by then, so the code reaches the caller with n_regions, which it reads to size
+ *   the table below.
+ *   B4D_EINVAL: both or neither input, a null pointer, batch < 1, an empty axis, connectivity not 1 or 2; B4D_ESIZE: ny * nx
+ *   >= 2^31 - 2048, ny > 2097120.
+ * b4d_region_properties: labels (batch, ny, nx) DEVICE int32 from any source (regions need not be connected); offsets (batch + 1)
+ *   HOST int32, offsets[0] = 0, ascending: frame t has the labels 1 .. offsets[t + 1] - offsets[t] and its rows start at
+ *   offsets[t]; pixels with another value belong to no region.  frames (batch, ny, nx) DEVICE float32 or NULL (geometry only).
+ *   out (offsets[batch], 20) DEVICE float64, per region
+ *     {area, y0, y1, x0, x1, cy, cx, sum, min, max, max_y, max_x, flux, wcy, wcx, var_y, var_x, cov_yx, n_nan, n_saturated}:
+ *     area: pixels.  [y0, y1) x [x0, x1): the bounding box.  cy, cx: the mean pixel position (integer sums, one division).
+ *     NaN pixels take no part in any value column and are counted in n_nan.  n_saturated: pixels with v >= saturation (+inf:
+ *     none).  sum = sum v; min, max; (max_y, max_x): the first occurrence of max in raster order.  w = max(v - background, 0);
+ *     flux = sum w; wcy = y0 + sum w (y - y0) / flux, wcx likewise; var_y = sum w (y - wcy)^2 / flux, var_x likewise, cov_yx =
+ *     sum w (y - wcy)(x - wcx) / flux, summed about the box corner; NaN in these five where flux is not > 0.
+ *     A region without a non-NaN pixel has NaN min / max, (-1, -1) as their position, sum 0.  A label without a pixel has area 0,
+ *     the box (0, 0, 0, 0), NaN centroids.  With frames == NULL sum, min, max, flux and the five are NaN, the position (-1, -1).
+ *   All arithmetic is float64 on the float32 pixels.  Every integer-valued column is exact; every column has the same bits run
+ *   to run, for a frame alone and in any batch: boxes by integer atomicMin / atomicMax (from the pixels on a region's outline),
+ *   then lane l of one wave (box area <= 4096) or of one 512-lane workgroup (above) adds the box pixels l, l + lanes, .. in
+ *   row-major order, a fixed butterfly joins the lanes of a wave, and the waves are added in order.  No float atomics.
+ *   Reads about 8 bytes per BOX pixel per pass (two passes where flux > 0): cheap for blobs, many reads of the frame for nested
+ *   frame-sized regions.  Scratch: 5 words per region.
+ *   B4D_EINVAL: null labels / offsets / out, batch < 1, an empty axis, offsets that do not start at 0 or descend, a background
+ *   that is not finite, a NaN saturation; B4D_ESIZE: ny * nx >= 2^31.
+ * b4d_relabel: out[p] = map[offsets[t] + labels[p] - 1] where 1 <= labels[p] <= offsets[t + 1] - offsets[t], else 0.  map
+ *   (offsets[batch]) DEVICE int32: old label -> new label, 0 drops the region.  out may be labels itself.                        */
+int b4d_label_regions(const float* frames, const float* thresholds, const unsigned char* mask, int batch, int ny, int nx,
+                      int connectivity, int32_t* labels, int32_t* n_regions, void* stream);
+int b4d_region_properties(const float* frames, const int32_t* labels, int batch, int ny, int nx, const int32_t* offsets,
+                          double background, double saturation, double* out, void* stream);
+int b4d_relabel(const int32_t* labels, int batch, int ny, int nx, const int32_t* offsets, const int32_t* map, int32_t* out,
+                void* stream);
 
 #ifdef __cplusplus
 }
