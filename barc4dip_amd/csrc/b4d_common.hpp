@@ -26,11 +26,11 @@ inline bool ranges_overlap(const void* a, size_t abytes, const void* b, size_t b
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
     return a && b && a0 < b0 + bbytes && b0 < a0 + abytes;
 }
-// lazily grown device scratch for second-stage reductions (b4d_stats.hip), one buffer per caller stream
+// lazily grown device scratch for second-stage reductions, one buffer per caller stream; defined in b4d_kernels.hip
 int get_scratch(size_t bytes, void** out, hipStream_t stream);
 // serialises the host side of every entry point that works in a scratch buffer (re-entrant calls from several host
 // threads, e.g. joblib workers, on one stream); device-side ordering comes from the stream, and different streams get
-// different buffers
+// different buffers.  Defined in b4d_kernels.hip
 std::recursive_mutex& scratch_mutex();
 #define B4D_SCRATCH_LOCK() std::lock_guard<std::recursive_mutex> b4d_scratch_lk__(::b4d::scratch_mutex())
 

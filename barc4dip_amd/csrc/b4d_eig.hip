@@ -33,36 +33,22 @@ constexpr int NB = 32;  // subspace width
 __global__ void __launch_bounds__(1024) k_sta2_sums(const float* __restrict__ x, size_t npix, double* __restrict__ part) {
     __shared__ double sh[16 * 3];
     const float* f = x + (size_t)blockIdx.y * npix;
-    double s = 0, q = 0, bad = 0;
+    double s[3] = {0, 0, 0};   // sum x, sum x^2, n_nonfinite
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (size_t)gridDim.x * blockDim.x) {
         const double v = f[i];
         if (isfinite(v)) {
-            s += v;
-            q = fma(v, v, q);
+            s[0] += v;
+            s[1] = fma(v, v, s[1]);
         } else {
-            bad += 1;
+            s[2] += 1;
         }
     }
-    s = wave_sum(s);
-    q = wave_sum(q);
-    bad = wave_sum(bad);
-    if ((threadIdx.x & 63) == 0) {
-        sh[(threadIdx.x >> 6) * 3] = s;
-        sh[(threadIdx.x >> 6) * 3 + 1] = q;
-        sh[(threadIdx.x >> 6) * 3 + 2] = bad;
-    }
-    __syncthreads();
+    block_sum(s, sh, 16);
     if (threadIdx.x == 0) {
-        double a = 0, b = 0, c = 0;
-        for (int i = 0; i < 16; ++i) {
-            a += sh[i * 3];
-            b += sh[i * 3 + 1];
-            c += sh[i * 3 + 2];
-        }
         double* o = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
-        o[0] = a;
-        o[1] = b;
-        o[2] = c;
+        o[0] = s[0];
+        o[1] = s[1];
+        o[2] = s[2];
     }
 }
 

@@ -5,6 +5,7 @@
 #include "b4d_wiener_mr.hpp"
 
 #include <cstring>
+#include <unordered_map>
 
 namespace b4d {
 std::string& last_error() {
@@ -53,6 +54,34 @@ int lane_stream(int idx, hipStream_t* out) {
     B4D_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     made.push_back(Made{dev, idx, st});
     *out = st;
+    return B4D_OK;
+}
+std::recursive_mutex& scratch_mutex() {
+    static std::recursive_mutex m;
+    return m;
+}
+// Lazily grown device scratch for second-stage reductions (never reallocated on the hot path once it has reached its high-water
+// mark).  One buffer per stream: the kernels of these entry points are asynchronous, so two streams sharing one scratch would
+// race on the device however well the host side is locked (the plans and the Wiener plan cache are per stream too).
+int get_scratch(size_t bytes, void** out, hipStream_t stream) {
+    struct StreamScratch {
+        void* p = nullptr;
+        size_t bytes = 0;
+    };
+    static std::mutex mu;
+    static std::unordered_map<hipStream_t, StreamScratch> per_stream;
+    std::lock_guard<std::mutex> lk(mu);
+    StreamScratch& sc = per_stream[stream];
+    if (bytes > sc.bytes) {
+        if (sc.p) (void)hipFree(sc.p);   // hipFree waits for the work that still uses the old buffer
+        sc.p = nullptr;
+        sc.bytes = 0;
+        const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
+        hipError_t e = hipMalloc(&sc.p, want);
+        if (e != hipSuccess) return fail(B4D_ENOMEM, std::string("scratch allocation: ") + hipGetErrorString(e));
+        sc.bytes = want;
+    }
+    *out = sc.p;
     return B4D_OK;
 }
 std::atomic<int> g_opt_track_predict{1};

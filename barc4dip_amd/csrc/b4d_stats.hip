@@ -1,17 +1,32 @@
-// b4d_stats.hip -- streaming reductions of the barc4dip metrics layer on gfx950:
-//   temporal per-pixel sums, finite-only distribution moments
-//   (metrics/statistics.py:17-125), Sobel / Laplace statistics with scipy "reflect"
-//   borders (metrics/sharpness.py:405-530).
-// All of them are HBM-bound single-read passes; float64 accumulation (the reference computes
-// these in float64), wave64 shuffles + one LDS hop per workgroup, and a fixed-order second
-// stage so results are bitwise reproducible (no float atomics).
+// b4d_stats.hip -- the streaming reductions of the metrics layer (DESIGN.md sections 4 and 33).  Every sum is float64, as the reference
+// computes them.  No float atomics except behind f95 (below): a workgroup combines its lanes with b4d_reduce.hpp (wave_sum, then the
+// wave sums in wave order from 0.0), writes its partial to its own slot of the per-stream scratch buffer, and a second launch
+// adds the slots in slot order.  The same call gives the same bits.
+//
+// b4d_temporal_accumulate[_range]: sx += sum_t x, sxx += sum_t x^2 per pixel.
+//   k_temporal_acc<PX>, grid ceil(npix / PX / 256), block 256: a lane owns PX adjacent pixels and walks the frames in order,
+//   a += x; q = fma(x, x, q).  PX = 4 (one 16-byte load per frame) where the range, the stride and the base allow it, else 1.
+// b4d_temporal_finalize[_dev]: k_temporal_fin, one lane per pixel: mean, variance (clamped at 0), contrast.
+// b4d_moments: finite-only distribution moments (metrics/statistics.py:17-125).
+//   k_moments1, grid (split, batch), block 1024: {n_finite, sum, n_zero, n_sat}; lane l of workgroup g takes the pixel groups
+//   g 1024 + l + k split 1024 in order.  k_moments2, same grid and map: the mean from the pass-1 slots in slot order, then
+//   {sum d^2, sum d^3, sum d^4}.  k_moments_fin, grid (batch): one lane adds the slots in slot order.
+// b4d_sobel_laplace_stats: scipy "reflect" borders (metrics/sharpness.py:405-530).
+//   k_sobel_lap, grid (ceil(nx / 64), ceil(ny / 16), batch), block 256: a lane walks 4 rows of one column in row order.
+//   k_sobel_fin, grid (batch), block 256: lane l adds the slots l, l + 256, .., then block_sum.
+// b4d_percentiles: np.nanpercentile, linear interpolation; exact radix select on the keys of b4d_keys.hpp (integer counts).
+//   k_percentiles, grid (batch), block 1024, below 2^17 pixels; k_pctm_hist / pick / clear0 / next / out over the whole chip above.
+// b4d_radial_profile: k_radial_profile, grid (nr, batch), block 256: lane l adds the angles l, l + 256, .., then block_sum.
+// b4d_psd_stats: disc sums, entropy sums and f95 of a shifted PSD map.
+//   k_psd_stats1, grid (256, batch), block 256: grid-stride over the bins, block_sum, one slot per workgroup; k_psd_stats_mid, one
+//   lane per map, adds the slots in slot order.  f95 alone comes from two float64 atomicAdd histograms (k_psd_stats1 coarse
+//   rings, k_psd_stats2 the exact r^2 inside the chosen ring; k_psd_stats_fin walks the latter): its sums depend on arrival order.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
-#include <mutex>
 #include <string>
-#include <unordered_map>
 
 #include "../../include/b4d.h"
 #include "b4d_common.hpp"
@@ -20,148 +35,55 @@
 
 namespace b4d {
 
-// ------------------------------------------------------------------------------------ scratch
-// Lazily grown per-process device scratch for second-stage reductions (never reallocated on the
-// hot path once it has reached its high-water mark).
-static std::mutex g_scratch_mu;
-struct StreamScratch {
-    void* p = nullptr;
-    size_t bytes = 0;
-};
-static std::unordered_map<hipStream_t, StreamScratch> g_stream_scratch;   // one lazily grown buffer per caller stream
-std::recursive_mutex& scratch_mutex() {
-    static std::recursive_mutex m;
-    return m;
-}
-// One buffer per stream: the kernels of these entry points are asynchronous, so two streams sharing one scratch would
-// race on the device however well the host side is locked (the plans and the Wiener plan cache are per stream too).
-int get_scratch(size_t bytes, void** out, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_scratch_mu);
-    StreamScratch& sc = g_stream_scratch[stream];
-    if (bytes > sc.bytes) {
-        if (sc.p) (void)hipFree(sc.p);   // hipFree waits for the work that still uses the old buffer
-        sc.p = nullptr;
-        sc.bytes = 0;
-        const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-        hipError_t e = hipMalloc(&sc.p, want);
-        if (e != hipSuccess) return fail(B4D_ENOMEM, std::string("scratch allocation: ") + hipGetErrorString(e));
-        sc.bytes = want;
-    }
-    *out = sc.p;
-    return B4D_OK;
-}
-
 // ------------------------------------------------------------------------------------ temporal
-// One lane owns 4 adjacent pixels (one 16-B load per frame); frames are walked with TU loads in flight.
-#ifndef B4D_TACC_UNROLL
-#define B4D_TACC_UNROLL 4
-#endif
-constexpr int TU = B4D_TACC_UNROLL;
 // Every frame word is read exactly once: streaming (non-temporal) loads keep the stack out of L2 -- 5.43 -> 5.94 TB/s on the
 // cfg4 shard (interleaved A/B, tools/dev_ab_temporal.py).
 typedef float tacc_f4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 tacc_load4(const float* p) {
-    const tacc_f4 q = __builtin_nontemporal_load(reinterpret_cast<const tacc_f4*>(p));
-    return make_float4(q.x, q.y, q.z, q.w);
+template <int PX>
+__device__ __forceinline__ void tacc_load(const float* p, float (&x)[PX]) {
+    if constexpr (PX == 4) {
+        const tacc_f4 q = __builtin_nontemporal_load(reinterpret_cast<const tacc_f4*>(p));
+        x[0] = q.x, x[1] = q.y, x[2] = q.z, x[3] = q.w;
+    } else {
+        x[0] = __builtin_nontemporal_load(p);
+    }
 }
-__global__ void __launch_bounds__(256) k_temporal_acc(const float* __restrict__ frames, int nframes, size_t npix,
+// A lane owns PX adjacent pixels of the range and walks the frames in order, four loads in flight.  `stride` = pixels from one
+// frame to the next (npix for whole contiguous frames).  PX = 4: one 16-byte load per frame; npix, stride and the base are
+// multiples of 4 pixels.  PX = 1: any pixel count / alignment (1023 x 1023 frames: odd rows start on odd dwords), dword loads
+// (still whole 256-byte lines per wave).
+template <int PX>
+__global__ void __launch_bounds__(256) k_temporal_acc(const float* __restrict__ frames, int nframes, size_t stride, size_t npix,
                                                       double* __restrict__ sx, double* __restrict__ sxx) {
-    const size_t i4 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i4 >= npix) return;
-    double a[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-    if (i4 + 3 < npix) {
-        const float* p = frames + i4;
-        int t = 0;
-        for (; t + TU <= nframes; t += TU) {
-            float4 v[TU];
-#pragma unroll
-            for (int k = 0; k < TU; ++k) v[k] = tacc_load4(p + (size_t)(t + k) * npix);
-#pragma unroll
-            for (int k = 0; k < TU; ++k) {
-                const double x0 = v[k].x, x1 = v[k].y, x2 = v[k].z, x3 = v[k].w;
-                a[0] += x0; a[1] += x1; a[2] += x2; a[3] += x3;
-                q[0] = fma(x0, x0, q[0]); q[1] = fma(x1, x1, q[1]); q[2] = fma(x2, x2, q[2]); q[3] = fma(x3, x3, q[3]);
-            }
-        }
-        for (; t < nframes; ++t) {
-            const float4 v = tacc_load4(p + (size_t)t * npix);
-            const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
-            a[0] += x0; a[1] += x1; a[2] += x2; a[3] += x3;
-            q[0] = fma(x0, x0, q[0]); q[1] = fma(x1, x1, q[1]); q[2] = fma(x2, x2, q[2]); q[3] = fma(x3, x3, q[3]);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            sx[i4 + k] += a[k];
-            sxx[i4 + k] += q[k];
-        }
-    } else {  // ragged tail
-        for (size_t i = i4; i < npix; ++i) {
-            double s = 0, ss = 0;
-            for (int t = 0; t < nframes; ++t) {
-                const double x = frames[(size_t)t * npix + i];
-                s += x;
-                ss = fma(x, x, ss);
-            }
-            sx[i] += s;
-            sxx[i] += ss;
-        }
-    }
-}
-
-// Any pixel count / alignment (1023 x 1023 frames: odd rows start on odd dwords): one lane per pixel, dword loads
-// (still whole 256-byte lines per wave), four frames in flight.  `stride` = pixels from one frame to the next.
-__global__ void __launch_bounds__(256) k_temporal_acc1(const float* __restrict__ frames, int nframes, size_t stride, size_t npix,
-                                                       double* __restrict__ sx, double* __restrict__ sxx) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * PX;
     if (i >= npix) return;
+    double a[PX] = {}, q[PX] = {};
     const float* p = frames + i;
-    double a = 0, q = 0;
-    int t = 0;
-    for (; t + 4 <= nframes; t += 4) {
-        float v[4];
+    auto take = [&](const float (&v)[PX]) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __builtin_nontemporal_load(p + (size_t)(t + k) * stride);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < PX; ++k) {
             const double x = v[k];
-            a += x;
-            q = fma(x, x, q);
+            a[k] += x;
+            q[k] = fma(x, x, q[k]);
         }
-    }
-    for (; t < nframes; ++t) {
-        const double x = p[(size_t)t * stride];
-        a += x;
-        q = fma(x, x, q);
-    }
-    sx[i] += a;
-    sxx[i] += q;
-}
-
-// 16-byte variant on a pixel range of strided frames (npix and every frame start a multiple of 4 pixels)
-__global__ void __launch_bounds__(256) k_temporal_acc4(const float* __restrict__ frames, int nframes, size_t stride, size_t npix,
-                                                       double* __restrict__ sx, double* __restrict__ sxx) {
-    const size_t i4 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if (i4 >= npix) return;
-    double a[4] = {0, 0, 0, 0}, q[4] = {0, 0, 0, 0};
-    const float* p = frames + i4;
-    auto take = [&](const float4& v) {
-        const double x0 = v.x, x1 = v.y, x2 = v.z, x3 = v.w;
-        a[0] += x0; a[1] += x1; a[2] += x2; a[3] += x3;
-        q[0] = fma(x0, x0, q[0]); q[1] = fma(x1, x1, q[1]); q[2] = fma(x2, x2, q[2]); q[3] = fma(x3, x3, q[3]);
     };
     int t = 0;
     for (; t + 4 <= nframes; t += 4) {
-        float4 v[4];
+        float v[4][PX];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = tacc_load4(p + (size_t)(t + k) * stride);
+        for (int k = 0; k < 4; ++k) tacc_load<PX>(p + (size_t)(t + k) * stride, v[k]);
 #pragma unroll
         for (int k = 0; k < 4; ++k) take(v[k]);
     }
-    for (; t < nframes; ++t) take(tacc_load4(p + (size_t)t * stride));
+    for (; t < nframes; ++t) {
+        float v[PX];
+        tacc_load<PX>(p + (size_t)t * stride, v);
+        take(v);
+    }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        sx[i4 + k] += a[k];
-        sxx[i4 + k] += q[k];
+    for (int k = 0; k < PX; ++k) {
+        sx[i + k] += a[k];
+        sxx[i + k] += q[k];
     }
 }
 
@@ -182,35 +104,36 @@ __global__ void __launch_bounds__(256) k_temporal_fin(const double* __restrict__
 
 // ------------------------------------------------------------------------------------ moments
 // pass 1: {n_finite, sum, n_zero, n_sat}; pass 2 (mean known): {sum d^2, sum d^3, sum d^4}
-// grid (split, batch).  partials: [batch][split][4] doubles.
+// grid (split, batch).  partials: [batch][split][4] doubles.  npix is a multiple of 4 (b4d_moments refuses any other).
+__device__ __forceinline__ void moments1_take(double x, double eps, double sat, double (&v)[4]) {
+    if (isfinite(x)) {
+        v[0] += 1.0;
+        v[1] += x;
+        v[2] += (fabs(x) <= eps) ? 1.0 : 0.0;
+        v[3] += (x >= sat) ? 1.0 : 0.0;
+    }
+}
+__device__ __forceinline__ void moments2_take(double x, double mu, double (&v)[3]) {
+    if (isfinite(x)) {
+        const double d = x - mu, d2 = d * d;
+        v[0] += d2;
+        v[1] = fma(d2, d, v[1]);
+        v[2] = fma(d2, d2, v[2]);
+    }
+}
+
 __global__ void __launch_bounds__(1024) k_moments1(const float* __restrict__ frames, size_t npix, double eps,
                                                    double sat, double* __restrict__ part) {
     __shared__ double sh[16 * 4];
-    const float* f = frames + (size_t)blockIdx.y * npix;
+    const float4* f = reinterpret_cast<const float4*>(frames + (size_t)blockIdx.y * npix);
     const size_t n4 = npix / 4;
     double v[4] = {0, 0, 0, 0};
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float4 q = reinterpret_cast<const float4*>(f)[i];
-        const float xs[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double x = xs[k];
-            if (isfinite(x)) {
-                v[0] += 1.0;
-                v[1] += x;
-                v[2] += (fabs(x) <= eps) ? 1.0 : 0.0;
-                v[3] += (x >= sat) ? 1.0 : 0.0;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (npix & 3)) {
-        const double x = f[n4 * 4 + threadIdx.x];
-        if (isfinite(x)) {
-            v[0] += 1.0;
-            v[1] += x;
-            v[2] += (fabs(x) <= eps) ? 1.0 : 0.0;
-            v[3] += (x >= sat) ? 1.0 : 0.0;
-        }
+        const float4 q = f[i];
+        moments1_take(q.x, eps, sat, v);
+        moments1_take(q.y, eps, sat, v);
+        moments1_take(q.z, eps, sat, v);
+        moments1_take(q.w, eps, sat, v);
     }
     block_sum(v, sh, (blockDim.x + 63) >> 6);
     __syncthreads();
@@ -236,31 +159,15 @@ __global__ void __launch_bounds__(1024) k_moments2(const float* __restrict__ fra
     }
     __syncthreads();
     const double mu = s_mean;
-    const float* f = frames + (size_t)blockIdx.y * npix;
+    const float4* f = reinterpret_cast<const float4*>(frames + (size_t)blockIdx.y * npix);
     const size_t n4 = npix / 4;
     double v[3] = {0, 0, 0};
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float4 q = reinterpret_cast<const float4*>(f)[i];
-        const float xs[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const double x = xs[k];
-            if (isfinite(x)) {
-                const double d = x - mu, d2 = d * d;
-                v[0] += d2;
-                v[1] = fma(d2, d, v[1]);
-                v[2] = fma(d2, d2, v[2]);
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (npix & 3)) {
-        const double x = f[n4 * 4 + threadIdx.x];
-        if (isfinite(x)) {
-            const double d = x - mu, d2 = d * d;
-            v[0] += d2;
-            v[1] = fma(d2, d, v[1]);
-            v[2] = fma(d2, d2, v[2]);
-        }
+        const float4 q = f[i];
+        moments2_take(q.x, mu, v);
+        moments2_take(q.y, mu, v);
+        moments2_take(q.z, mu, v);
+        moments2_take(q.w, mu, v);
     }
     block_sum(v, sh, (blockDim.x + 63) >> 6);
     __syncthreads();
@@ -292,20 +199,20 @@ __global__ void k_moments_fin(const double* __restrict__ p1, const double* __res
 // scipy.ndimage "reflect" = half-sample symmetric: index -1 -> 0, n -> n-1.
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i - 1 : (i >= n ? 2 * n - 1 - i : i); }
 
-// grid (ceil(nx/64), ceil(ny/16), batch), block (64, 4): each thread walks 4 rows of one column.
+// grid (ceil(nx/64), ceil(ny/16), batch), block 256 = 64 columns x 4 row groups: each thread walks 4 rows of one column.
 // partials [batch][gridDim.y*gridDim.x][5] = {n_finite, sum gx^2, sum gy^2, sum lap, sum lap^2}
 __global__ void __launch_bounds__(256) k_sobel_lap(const float* __restrict__ frames, int ny, int nx,
                                                    double* __restrict__ part) {
     __shared__ double sh[16 * 5];
     const float* f = frames + (size_t)blockIdx.z * ny * nx;
-    const int x = blockIdx.x * 64 + threadIdx.x;
-    const int tid = threadIdx.y * 64 + threadIdx.x;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    const int x = blockIdx.x * 64 + tx;
     double v[5] = {0, 0, 0, 0, 0};
     if (x < nx) {
         const int xm = refl(x - 1, nx), xp = refl(x + 1, nx);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int y = blockIdx.y * 16 + threadIdx.y * 4 + r;
+            const int y = blockIdx.y * 16 + ty * 4 + r;
             if (y >= ny) break;
             const int ym = refl(y - 1, ny), yp = refl(y + 1, ny);
             const float* rm = f + (size_t)ym * nx;
@@ -327,20 +234,11 @@ __global__ void __launch_bounds__(256) k_sobel_lap(const float* __restrict__ fra
             }
         }
     }
-    // block_sum indexes by threadIdx.x; flatten the 2-D block
-    {
-        const int lane = tid & 63, w = tid >> 6;
+    block_sum(v, sh, 4);
+    if (threadIdx.x == 0) {
+        double* o = part + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 5;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            v[k] = wave_sum(v[k]);
-            if (lane == 0) sh[w * 5 + k] = v[k];
-        }
-        __syncthreads();
-        if (tid == 0) {
-            double* o = part + (((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 5;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) o[k] = sh[k] + sh[5 + k] + sh[10 + k] + sh[15 + k];
-        }
+        for (int k = 0; k < 5; ++k) o[k] = v[k];
     }
 }
 
@@ -386,15 +284,27 @@ __device__ __forceinline__ unsigned pct_rank(double vi, unsigned n) {   // n >= 
     if (!(f > 0.0)) return 0u;
     return f >= (double)(n - 1) ? n - 1 : (unsigned)f;
 }
+// one output row {lo value, hi value, fraction, n_valid} from the virtual index and the keys of the two order statistics; no valid
+// pixel (n == 0, the other arguments unused): {NaN, NaN, 0, 0}
+__device__ __forceinline__ void pct_write_row(double* o, unsigned n, double vi, unsigned ka, unsigned kb) {
+    if (n == 0) {
+        o[0] = o[1] = nan("");
+        o[2] = 0.0;
+        o[3] = 0.0;
+        return;
+    }
+    o[0] = (double)keys::from_key(ka);
+    o[1] = (double)keys::from_key(kb);
+    o[2] = vi - floor(vi);
+    o[3] = (double)n;
+}
+
+constexpr int PCT_REP = 4;   // replicated histograms: intensity data crowd a few exponent bins (b4d_select.hpp)
 
 // grid (batch), block 1024.
 __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ frames, size_t npix, const double* __restrict__ q,
                                                       int nq, double* __restrict__ out) {
-#ifndef B4D_PCT_REP
-#define B4D_PCT_REP 4
-#endif
-    constexpr int REP = B4D_PCT_REP;   // replicated histograms: intensity data crowd a few exponent bins (b4d_select.hpp)
-    __shared__ unsigned hist[2048 * REP];
+    __shared__ unsigned hist[2048 * PCT_REP];
     __shared__ unsigned sh[4];
     __shared__ unsigned s_cnt[16];
     const float* x = frames + (size_t)blockIdx.x * npix;
@@ -410,22 +320,17 @@ __global__ void __launch_bounds__(1024) k_percentiles(const float* __restrict__ 
     for (int iq = 0; iq < nq; ++iq) {
         double* o = out + ((size_t)blockIdx.x * nq + iq) * 4;
         if (n == 0) {
-            if (threadIdx.x == 0) o[0] = o[1] = nan(""), o[2] = 0.0, o[3] = 0.0;
+            if (threadIdx.x == 0) pct_write_row(o, 0, 0.0, 0, 0);
             continue;
         }
         const double vi = pct_virtual_index(q[iq], n);
         const unsigned lo = pct_rank(vi, n);
         const unsigned hi = lo + 1 < n ? lo + 1 : n - 1;
         unsigned nl, ne;
-        const unsigned ka = radix_select<REP>(x, n_all, lo, hist, sh, nl, ne);
+        const unsigned ka = radix_select<PCT_REP>(x, n_all, lo, hist, sh, nl, ne);
         unsigned kb = ka;
         if (hi != lo && nl + ne <= hi) kb = next_larger_key(x, n_all, ka, hist);
-        if (threadIdx.x == 0) {
-            o[0] = (double)keys::from_key(ka);
-            o[1] = (double)keys::from_key(kb);
-            o[2] = vi - floor(vi);
-            o[3] = (double)n;
-        }
+        if (threadIdx.x == 0) pct_write_row(o, n, vi, ka, kb);
         __syncthreads();
     }
 }
@@ -446,7 +351,7 @@ struct PctMulti {
 // pass: 0, 1, 2 (bits 31..21, 20..10, 9..0).  grid (NB, batch, pass == 0 ? 1 : nq), block 256
 template <int PASS>
 __global__ void __launch_bounds__(256) k_pctm_hist(PctMulti p) {
-    constexpr int REP = 4;
+    constexpr int REP = PCT_REP;
     __shared__ unsigned hist[2048 * REP];
     const int f = blockIdx.y, j = blockIdx.z;
     constexpr int sft = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0), nb = PASS == 2 ? 1024 : 2048;
@@ -517,22 +422,11 @@ __global__ void __launch_bounds__(64) k_pctm_out(PctMulti p) {
     const int f = blockIdx.x, j = threadIdx.x;
     if (j >= p.nq) return;
     const unsigned* st = p.state + ((size_t)f * p.nq + j) * 8;
-    double* o = p.out + ((size_t)f * p.nq + j) * 4;
     const unsigned n = st[4];
-    if (n == 0) {
-        o[0] = o[1] = nan("");
-        o[2] = 0.0;
-        o[3] = 0.0;
-        return;
-    }
-    const double vi = pct_virtual_index(p.q[j], n);
-    const unsigned lo = st[2], hi = lo + 1 < n ? lo + 1 : n - 1;
+    const unsigned lo = st[2], hi = lo + 1 < n ? lo + 1 : n - 1;   // n == 0: unused
     unsigned kb = st[0];
     if (hi != lo && st[1] + st[3] <= hi && st[5] != 0xffffffffu) kb = st[5];
-    o[0] = (double)keys::from_key(st[0]);
-    o[1] = (double)keys::from_key(kb);
-    o[2] = vi - floor(vi);
-    o[3] = (double)n;
+    pct_write_row(p.out + ((size_t)f * p.nq + j) * 4, n, pct_virtual_index(p.q[j], n), st[0], kb);
 }
 
 // ------------------------------------------------------------------------------------ radial profile
@@ -547,7 +441,7 @@ __global__ void __launch_bounds__(256) k_radial_profile(const float* __restrict_
     const double r = nr > 1 ? (ir == nr - 1 ? r_max : (double)ir * (r_max / (double)(nr - 1))) : 0.0;
     const double x0 = -(double)(nx / 2), x1 = (double)(nx - 1 - nx / 2), y0 = -(double)(ny / 2), y1 = (double)(ny - 1 - ny / 2);
     const double two_pi = 6.283185307179586476925286766559;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int it = threadIdx.x; it < ntheta; it += blockDim.x) {
         const double th = (double)it * (two_pi / (double)ntheta);
         const double px = r * cos(th), py = r * sin(th);
@@ -562,12 +456,10 @@ __global__ void __launch_bounds__(256) k_radial_profile(const float* __restrict_
             const double v00 = p[0], v01 = p[1], v10 = p[nx], v11 = p[nx + 1];
             val = (1.0 - ty) * ((1.0 - tx) * v00 + tx * v01) + ty * ((1.0 - tx) * v10 + tx * v11);
         }
-        acc += val;
+        acc[0] += val;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[(size_t)blockIdx.y * nr + ir] = (sh[0] + sh[1] + sh[2] + sh[3]) / (double)ntheta;
+    block_sum(acc, sh, 4);
+    if (threadIdx.x == 0) out[(size_t)blockIdx.y * nr + ir] = acc[0] / (double)ntheta;
 }
 
 // ------------------------------------------------------------------------------------ PSD statistics
@@ -587,11 +479,28 @@ struct PsdStatArgs {
     int ncoarse, nfine;
 };
 
-__device__ __forceinline__ void psd_coords(int i, int j, int ny, int nx, double& fx, double& fy, long long& r2) {
-    const int dy = i - ny / 2, dx = j - nx / 2;
-    fx = (double)dx / (double)nx;
-    fy = (double)dy / (double)ny;
-    r2 = (long long)dx * dx + (long long)dy * dy;
+// offsets of bin e from the DC bin; returns the integer radius^2
+__device__ __forceinline__ long long psd_offsets(size_t e, int ny, int nx, int& dy, int& dx) {
+    dy = (int)(e / nx) - ny / 2;
+    dx = (int)(e % nx) - nx / 2;
+    return (long long)dx * dx + (long long)dy * dy;
+}
+// the sample of bin e: p with the DC bin and non-finite values zeroed (np.nan_to_num(..., 0)), the frequencies, the integer radius^2
+struct PsdBin {
+    double p, fx, fy, fr;
+    long long r2;
+};
+__device__ __forceinline__ PsdBin psd_bin(const float* P, size_t e, int ny, int nx) {
+    int dy, dx;
+    PsdBin b;
+    b.r2 = psd_offsets(e, ny, nx, dy, dx);
+    b.p = (double)P[e];
+    if (dy == 0 && dx == 0) b.p = 0.0;
+    if (!isfinite(b.p)) b.p = 0.0;
+    b.fx = (double)dx / (double)nx;
+    b.fy = (double)dy / (double)ny;
+    b.fr = sqrt(__dadd_rn(__dmul_rn(b.fx, b.fx), __dmul_rn(b.fy, b.fy)));
+    return b;
 }
 
 // pass 1: partial sums + coarse radial histogram (bin = floor(sqrt(r2)), square maps).  grid (nblk, batch), block 256
@@ -604,25 +513,18 @@ __global__ void __launch_bounds__(256) k_psd_stats1(PsdStatArgs a, double fmax) 
     double v[7] = {0, 0, 0, 0, 0, 0, 0};
     const size_t n = (size_t)a.ny * a.nx;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const int i = (int)(e / a.nx), j = (int)(e % a.nx);
-        double p = (double)P[e];
-        if (i == a.ny / 2 && j == a.nx / 2) p = 0.0;
-        if (!isfinite(p)) p = 0.0;  // np.nan_to_num(..., 0)
-        double fx, fy;
-        long long r2;
-        psd_coords(i, j, a.ny, a.nx, fx, fy, r2);
-        const double fr2 = __dadd_rn(__dmul_rn(fx, fx), __dmul_rn(fy, fy));
-        const double fr = sqrt(fr2);
+        const PsdBin s = psd_bin(P, e, a.ny, a.nx);
+        const double p = s.p;
         v[5] += p;
         if (p > 0.0) v[6] = fma(p, log(p), v[6]);
-        if (fr <= fmax) {
+        if (s.fr <= fmax) {
             v[0] += p;
-            v[1] = fma(__dmul_rn(fr, fr), p, v[1]);
-            v[2] = fma(__dmul_rn(fx, fx), p, v[2]);
-            v[3] = fma(__dmul_rn(fy, fy), p, v[3]);
+            v[1] = fma(__dmul_rn(s.fr, s.fr), p, v[1]);
+            v[2] = fma(__dmul_rn(s.fx, s.fx), p, v[2]);
+            v[3] = fma(__dmul_rn(s.fy, s.fy), p, v[3]);
             v[4] = fma(p, p, v[4]);
             if (a.ncoarse > 0) {
-                int b = (int)floor(sqrt((double)r2));
+                int b = (int)floor(sqrt((double)s.r2));
                 b = b < a.ncoarse ? b : a.ncoarse - 1;
                 atomicAdd(&lhist[b], p);
             }
@@ -679,19 +581,13 @@ __global__ void __launch_bounds__(256) k_psd_stats2(PsdStatArgs a, double fmax) 
     __syncthreads();
     const size_t n = (size_t)a.ny * a.nx;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
-        const int i = (int)(e / a.nx), j = (int)(e % a.nx);
-        double fx, fy;
-        long long r2;
-        psd_coords(i, j, a.ny, a.nx, fx, fy, r2);
-        const long long d = r2 - lo;
+        int dy, dx;
+        const long long r2 = psd_offsets(e, a.ny, a.nx, dy, dx), d = r2 - lo;   // nearly every bin leaves here, unread
         if (d < 0 || d >= a.nfine) continue;
         if ((int)floor(sqrt((double)r2)) != R) continue;
-        const double fr = sqrt(__dadd_rn(__dmul_rn(fx, fx), __dmul_rn(fy, fy)));
-        if (!(fr <= fmax)) continue;
-        double p = (double)P[e];
-        if (i == a.ny / 2 && j == a.nx / 2) p = 0.0;
-        if (!isfinite(p)) p = 0.0;
-        if (p != 0.0) atomicAdd(&lhist[(int)d], p);
+        const PsdBin s = psd_bin(P, e, a.ny, a.nx);
+        if (!(s.fr <= fmax)) continue;
+        if (s.p != 0.0) atomicAdd(&lhist[(int)d], s.p);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < a.nfine; i += blockDim.x)
@@ -707,18 +603,13 @@ __global__ void k_psd_stats_fin(PsdStatArgs a, const int* __restrict__ ring, con
     const long long lo = (long long)ring[b] * ring[b];
     double cum = below[b];
     long long r2 = lo;
-    bool found = false;
     for (int i = 0; i < a.nfine; ++i) {
         const double c = a.fine[(size_t)b * a.nfine + i];
         if (c == 0.0) continue;
         r2 = lo + i;
-        if ((cum + c) / tot >= 0.95) {
-            found = true;
-            break;
-        }
+        if ((cum + c) / tot >= 0.95) break;
         cum += c;
     }
-    (void)found;
     // no power inside the disc (an all-zero map): there is no 95 % radius
     out[(size_t)b * 8 + 7] = tot > 0.0 ? sqrt((double)r2) / (double)a.nx : nan("");
 }
@@ -741,19 +632,16 @@ int b4d_temporal_accumulate_range(const float* frames, int nframes, size_t frame
     if (!frames || !sum_x || !sum_xx) return fail(B4D_EINVAL, "null argument");
     if (nframes < 1 || npix < 1 || pix0 + npix > frame_stride) return fail(B4D_EINVAL, "bad frame count or pixel range");
     const float* f0 = frames + pix0;
+    hipStream_t st = (hipStream_t)stream;
     if ((reinterpret_cast<uintptr_t>(f0) & 15) == 0 && (npix & 3) == 0 && (frame_stride & 3) == 0) {
-        if (pix0 == 0 && npix == frame_stride) {   // whole contiguous frames: the original kernel (ragged tail handled inside)
-            hipLaunchKernelGGL(k_temporal_acc, dim3((unsigned)((npix / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, frames, nframes,
-                               npix, sum_x, sum_xx);
-        } else {
-            hipLaunchKernelGGL(k_temporal_acc4, dim3((unsigned)((npix / 4 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f0, nframes,
-                               frame_stride, npix, sum_x, sum_xx);
-        }
+        if (const int rc = launch(k_temporal_acc<4>, dim3((unsigned)((npix / 4 + 255) / 256)), dim3(256), 0, st, f0, nframes, frame_stride,
+                                  npix, sum_x, sum_xx))
+            return rc;
     } else {   // odd pixel counts / unaligned views (the reference's data.mean(axis=0) takes any shape, io/rw.py:129-132)
-        hipLaunchKernelGGL(k_temporal_acc1, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, f0, nframes,
-                           frame_stride, npix, sum_x, sum_xx);
+        if (const int rc = launch(k_temporal_acc<1>, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, f0, nframes, frame_stride,
+                                  npix, sum_x, sum_xx))
+            return rc;
     }
-    B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
 
@@ -761,18 +649,18 @@ int b4d_temporal_finalize(const double* sum_x, const double* sum_xx, double coun
                           float* var, float* contrast, void* stream) {
     if (!sum_x || !sum_xx) return fail(B4D_EINVAL, "null argument");
     if (!(count > 0)) return fail(B4D_EINVAL, "count must be > 0");
-    hipLaunchKernelGGL(k_temporal_fin, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sum_x,
-                       sum_xx, count, (const double*)nullptr, npix, mean, var, contrast);
-    B4D_HIP(hipGetLastError());
+    if (const int rc = launch(k_temporal_fin, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sum_x, sum_xx, count,
+                              nullptr, npix, mean, var, contrast))
+        return rc;
     return B4D_OK;
 }
 
 int b4d_temporal_finalize_dev(const double* sum_x, const double* sum_xx, const double* count_dev, size_t npix, float* mean,
                               float* var, float* contrast, void* stream) {
     if (!sum_x || !sum_xx || !count_dev) return fail(B4D_EINVAL, "null argument");
-    hipLaunchKernelGGL(k_temporal_fin, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sum_x,
-                       sum_xx, 0.0, count_dev, npix, mean, var, contrast);
-    B4D_HIP(hipGetLastError());
+    if (const int rc = launch(k_temporal_fin, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, (hipStream_t)stream, sum_x, sum_xx, 0.0,
+                              count_dev, npix, mean, var, contrast))
+        return rc;
     return B4D_OK;
 }
 
@@ -787,16 +675,14 @@ int b4d_moments(const float* frames, int batch, size_t npix, double eps, double 
     split = split < 1 ? 1 : (split > 256 ? 256 : split);
     const size_t work = (npix / 4 + 1023) / 1024;
     if ((size_t)split > work) split = (int)(work ? work : 1);
+    hipStream_t st = (hipStream_t)stream;
     void* ws = nullptr;
-    int rc = get_scratch(sizeof(double) * 7 * (size_t)batch * split, &ws, (hipStream_t)stream);
-    if (rc) return rc;
+    if (const int rc = get_scratch(sizeof(double) * 7 * (size_t)batch * split, &ws, st)) return rc;
     double* p1 = static_cast<double*>(ws);
     double* p2 = p1 + (size_t)4 * batch * split;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_moments1, dim3(split, batch), dim3(1024), 0, st, frames, npix, eps, saturation, p1);
-    hipLaunchKernelGGL(k_moments2, dim3(split, batch), dim3(1024), 0, st, frames, npix, p1, split, p2);
-    hipLaunchKernelGGL(k_moments_fin, dim3(batch), dim3(64), 0, st, p1, p2, split, out);
-    B4D_HIP(hipGetLastError());
+    if (const int rc = launch(k_moments1, dim3(split, batch), dim3(1024), 0, st, frames, npix, eps, saturation, p1)) return rc;
+    if (const int rc = launch(k_moments2, dim3(split, batch), dim3(1024), 0, st, frames, npix, p1, split, p2)) return rc;
+    if (const int rc = launch(k_moments_fin, dim3(batch), dim3(64), 0, st, p1, p2, split, out)) return rc;
     return B4D_OK;
 }
 
@@ -806,16 +692,14 @@ int b4d_sobel_laplace_stats(const float* frames, int batch, int ny, int nx, doub
     if (batch < 1 || ny < 1 || nx < 1) return fail(B4D_EINVAL, "batch, ny, nx must be >= 1");
     const dim3 grid((nx + 63) / 64, (ny + 15) / 16, batch);
     const int nblk = grid.x * grid.y;
-    void* ws = nullptr;
-    int rc = get_scratch(sizeof(double) * 5 * (size_t)batch * nblk, &ws, (hipStream_t)stream);
-    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_sobel_lap, grid, dim3(64, 4), 0, st, frames, ny, nx, static_cast<double*>(ws));
-    hipLaunchKernelGGL(k_sobel_fin, dim3(batch), dim3(256), 0, st, static_cast<const double*>(ws), nblk, out);
-    B4D_HIP(hipGetLastError());
+    void* ws = nullptr;
+    if (const int rc = get_scratch(sizeof(double) * 5 * (size_t)batch * nblk, &ws, st)) return rc;
+    double* part = static_cast<double*>(ws);
+    if (const int rc = launch(k_sobel_lap, grid, dim3(256), 0, st, frames, ny, nx, part)) return rc;
+    if (const int rc = launch(k_sobel_fin, dim3(batch), dim3(256), 0, st, part, nblk, out)) return rc;
     return B4D_OK;
 }
-
 
 int b4d_percentiles(const float* frames, int batch, size_t npix, const double* q_host, int nq, double* out,
                     void* stream) {
@@ -827,12 +711,12 @@ int b4d_percentiles(const float* frames, int batch, size_t npix, const double* q
     const bool multi = npix >= ((size_t)1 << 17);
     const size_t hist_words = multi ? (size_t)batch * nq * 2048 : 0, state_words = multi ? (size_t)batch * nq * 8 : 0;
     void* ws = nullptr;
-    int rc = get_scratch(sizeof(double) * 16 + sizeof(unsigned) * (hist_words + state_words), &ws, (hipStream_t)stream);
-    if (rc) return rc;
+    if (const int rc = get_scratch(sizeof(double) * 16 + sizeof(unsigned) * (hist_words + state_words), &ws, st)) return rc;
     B4D_HIP(hipMemcpyAsync(ws, q_host, sizeof(double) * nq, hipMemcpyHostToDevice, st));
     B4D_HIP(hipStreamSynchronize(st));
     if (!multi) {
-        hipLaunchKernelGGL(k_percentiles, dim3(batch), dim3(1024), 0, st, frames, npix, static_cast<const double*>(ws), nq, out);
+        if (const int rc = launch(k_percentiles, dim3(batch), dim3(1024), 0, st, frames, npix, static_cast<const double*>(ws), nq, out))
+            return rc;
     } else {  // large frames: every pass of the radix select runs on the whole chip
         PctMulti pm{};
         pm.frames = frames;
@@ -844,17 +728,16 @@ int b4d_percentiles(const float* frames, int batch, size_t npix, const double* q
         pm.nq = nq;
         const int nbw = (int)std::min<size_t>(256, (npix / 4 + 255) / 256);
         B4D_HIP(hipMemsetAsync(pm.hist, 0, sizeof(unsigned) * (hist_words + state_words), st));
-        hipLaunchKernelGGL((k_pctm_hist<0>), dim3(nbw, batch, 1), dim3(256), 0, st, pm);
-        hipLaunchKernelGGL((k_pctm_pick<0>), dim3(batch, nq), dim3(64), 0, st, pm);
-        hipLaunchKernelGGL(k_pctm_clear0, dim3(batch), dim3(256), 0, st, pm);
-        hipLaunchKernelGGL((k_pctm_hist<1>), dim3(nbw, batch, nq), dim3(256), 0, st, pm);
-        hipLaunchKernelGGL((k_pctm_pick<1>), dim3(batch, nq), dim3(64), 0, st, pm);
-        hipLaunchKernelGGL((k_pctm_hist<2>), dim3(nbw, batch, nq), dim3(256), 0, st, pm);
-        hipLaunchKernelGGL((k_pctm_pick<2>), dim3(batch, nq), dim3(64), 0, st, pm);
-        hipLaunchKernelGGL(k_pctm_next, dim3(nbw, batch, nq), dim3(256), 0, st, pm);
-        hipLaunchKernelGGL(k_pctm_out, dim3(batch), dim3(64), 0, st, pm);
+        if (const int rc = launch(k_pctm_hist<0>, dim3(nbw, batch, 1), dim3(256), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_pick<0>, dim3(batch, nq), dim3(64), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_clear0, dim3(batch), dim3(256), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_hist<1>, dim3(nbw, batch, nq), dim3(256), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_pick<1>, dim3(batch, nq), dim3(64), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_hist<2>, dim3(nbw, batch, nq), dim3(256), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_pick<2>, dim3(batch, nq), dim3(64), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_next, dim3(nbw, batch, nq), dim3(256), 0, st, pm)) return rc;
+        if (const int rc = launch(k_pctm_out, dim3(batch), dim3(64), 0, st, pm)) return rc;
     }
-    B4D_HIP(hipGetLastError());
     B4D_HIP(hipStreamSynchronize(st));  // the shared scratch holds q (and the selection state) until the kernels have run
     return B4D_OK;
 }
@@ -864,8 +747,8 @@ int b4d_radial_profile(const float* maps, int batch, int ny, int nx, int nr, int
     B4D_SCRATCH_LOCK();
     if (!maps || !out) return fail(B4D_EINVAL, "null argument");
     if (batch < 1 || ny < 2 || nx < 2 || nr < 2 || ntheta < 4 || !(r_max > 0)) return fail(B4D_EINVAL, "bad shape / sampling");
-    hipLaunchKernelGGL(k_radial_profile, dim3(nr, batch), dim3(256), 0, (hipStream_t)stream, maps, ny, nx, nr, ntheta, r_max, out);
-    B4D_HIP(hipGetLastError());
+    if (const int rc = launch(k_radial_profile, dim3(nr, batch), dim3(256), 0, (hipStream_t)stream, maps, ny, nx, nr, ntheta, r_max, out))
+        return rc;
     return B4D_OK;
 }
 
@@ -884,10 +767,8 @@ int b4d_psd_stats(const float* psd, int batch, int ny, int nx, double* out, void
     a.nfine = square ? 2 * (nx / 2 + 2) + 1 : 0;
     const size_t nd = (size_t)batch * (8 * a.nblk + a.ncoarse + a.nfine + 2) + 64;
     void* ws = nullptr;
-    int rc = get_scratch(sizeof(double) * nd + sizeof(int) * batch, &ws, (hipStream_t)stream);
-    if (rc) return rc;
-    double* base = static_cast<double*>(ws);
-    a.part = base;
+    if (const int rc = get_scratch(sizeof(double) * nd + sizeof(int) * batch, &ws, st)) return rc;
+    a.part = static_cast<double*>(ws);
     a.coarse = a.part + (size_t)batch * 8 * a.nblk;
     a.fine = a.coarse + (size_t)batch * a.ncoarse;
     double* below = a.fine + (size_t)batch * a.nfine;
@@ -899,13 +780,12 @@ int b4d_psd_stats(const float* psd, int batch, int ny, int nx, double* out, void
     const double fmax = std::fmin(amax(nx), amax(ny));
     // dynamic LDS of the ring histograms, square maps only; nx has no upper limit at this entry point: k_psd_stats1 takes
     // 8 (nx / 2 + 2) bytes (64 KiB passed from nx = 16 382), k_psd_stats2 8 (nx + 5) bytes (passed from nx = 8 188)
-    if ((rc = launch(k_psd_stats1, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.ncoarse, st, a, fmax))) return rc;
-    hipLaunchKernelGGL(k_psd_stats_mid, dim3(batch), dim3(64), 0, st, a, out, ring, below);
+    if (const int rc = launch(k_psd_stats1, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.ncoarse, st, a, fmax)) return rc;
+    if (const int rc = launch(k_psd_stats_mid, dim3(batch), dim3(64), 0, st, a, out, ring, below)) return rc;
     if (square) {
-        if ((rc = launch(k_psd_stats2, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.nfine, st, a, fmax))) return rc;
-        hipLaunchKernelGGL(k_psd_stats_fin, dim3(batch), dim3(64), 0, st, a, ring, below, out);
+        if (const int rc = launch(k_psd_stats2, dim3(a.nblk, batch), dim3(256), sizeof(double) * a.nfine, st, a, fmax)) return rc;
+        if (const int rc = launch(k_psd_stats_fin, dim3(batch), dim3(64), 0, st, a, ring, below, out)) return rc;
     }
-    B4D_HIP(hipGetLastError());
     return B4D_OK;
 }
 

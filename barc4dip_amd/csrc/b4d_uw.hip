@@ -87,16 +87,12 @@ __global__ void __launch_bounds__(256) k_uw_step(UwArgs p) {
             }
         }
     }
-    __shared__ double sh[4][4];
+    __shared__ double sh[4 * 4];
     double v[4] = {q1, q2, d1, d2};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        v[k] = wave_sum(v[k]);
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = v[k];
-    }
-    __syncthreads();
-    // (not block_sum_columns of b4d_reduce.hpp: this combine starts from the first wave's sum, not from 0.0)
-    if (threadIdx.x < 4) p.part[(size_t)blockIdx.x * 4 + threadIdx.x] = sh[0][threadIdx.x] + sh[1][threadIdx.x] + sh[2][threadIdx.x] + sh[3][threadIdx.x];
+    // Every lane accumulator here starts at +0.0 and only adds.  So no lane value, wave sum or LDS row is ever -0.0, and
+    // 0.0 + s0 + s1 + .. equals s0 + s1 + .. exactly.
+    const double s = block_sum_columns(v, sh, 4);
+    if (threadIdx.x < 4) p.part[(size_t)blockIdx.x * 4 + threadIdx.x] = s;
 }
 
 // fixed-order sum of the block partials: the same call gives the same sums bit for bit
@@ -130,8 +126,7 @@ extern "C" int b4d_uw_step(const void* y, const void* tf, const float* areg2, vo
     const int nblk = (int)std::min<size_t>((n + 255) / 256, 2048);
     B4D_SCRATCH_LOCK();
     void* scratch = nullptr;
-    int rc = get_scratch(sizeof(double) * 4 * (size_t)nblk, &scratch, st);
-    if (rc) return rc;
+    if (const int rc = get_scratch(sizeof(double) * 4 * (size_t)nblk, &scratch, st)) return rc;
     UwArgs a{};
     a.y = static_cast<const float2*>(y);
     a.h = static_cast<const float2*>(tf);
@@ -149,8 +144,7 @@ extern "C" int b4d_uw_step(const void* y, const void* tf, const float* areg2, vo
     a.nxh = nxh;
     a.herm = nxh != ny ? 1 : 0;
     a.part = static_cast<double*>(scratch);
-    hipLaunchKernelGGL(k_uw_step, dim3(nblk), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_uw_sum, dim3(1), dim3(64), 0, st, (const double*)a.part, nblk, sums4);
-    B4D_HIP(hipGetLastError());
+    if (const int rc = launch(k_uw_step, dim3(nblk), dim3(256), 0, st, a)) return rc;
+    if (const int rc = launch(k_uw_sum, dim3(1), dim3(64), 0, st, a.part, nblk, sums4)) return rc;
     return B4D_OK;
 }

@@ -154,7 +154,7 @@ def test_temporal_stats_packed_allreduce_and_row_block_overlap():
 
 
 def test_reduction_entry_points_on_two_streams(K):
-    """The second-stage reduction scratch is per stream (csrc/b4d_stats.hip: get_scratch): calls queued on two torch
+    """The second-stage reduction scratch is per stream (csrc/b4d_kernels.hip: get_scratch): calls queued on two torch
     streams, interleaved without any host synchronisation in between, must give the serial results."""
     import torch
 

@@ -492,6 +492,25 @@ def test_temporal_accumulate_range_direct(env, T):
             run(pix0, npix)
 
 
+def test_temporal_accumulate_range_two_workgroups(env):
+    """1028 pixels are 257 groups of four: two workgroups of the 16-byte kernel, the second with one live lane; five of the dword
+    kernel on the unaligned range."""
+    T, stride = 5, 1028
+    stack = _edge_stack(T, (4, 257), 71)
+    t = _dev(env, stack.reshape(T, stride))
+    assert t.data_ptr() % 16 == 0
+    for pix0, npix in ((0, 1028), (4, 1024), (1, 1027)):
+        acc = env.torch.full((2, npix + 8), -3.0, dtype=env.torch.float64, device="cuda")
+        acc[:, 4:4 + npix] = 0.0
+        env.ffi.check(env.lib.b4d_temporal_accumulate_range(env.D.ptr(t), T, stride, pix0, npix, env.D.ptr(acc[0, 4:]),
+                                                            env.D.ptr(acc[1, 4:]), env.ffi.stream_ptr()))
+        a = acc.cpu().numpy()
+        sx, sxx = SN.temporal_sums_range(stack, pix0, npix)
+        np.testing.assert_array_equal(a[0, 4:4 + npix], sx, err_msg=f"{pix0}+{npix}")
+        np.testing.assert_array_equal(a[1, 4:4 + npix], sxx, err_msg=f"{pix0}+{npix}")
+        assert np.all(a[:, :4] == -3.0) and np.all(a[:, 4 + npix:] == -3.0)               # nothing written around the range
+
+
 def test_temporal_finalize_count_and_null_outputs(env):
     T = 5
     stack = _edge_stack(T, (6, 10), 9)
